@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- SRCNN Y-channel 2x throughput on MI355X (the metric BASELINE.json names).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the roofline of the
+dominant kernel (from HIP events recorded inside the timed steps) and the HBM traffic of the committed profile.
+Everything that takes runs of its own -- the CPU baseline, the other generator, the non-parity tiers, the PCIe-inclusive
+stream, ProcessSRCNN wall times, BASELINE configs #2-#4, the event-timed and clock-probed steps, and at N > 1 the RCCL
+probe -- runs only with --full.  --dump-outputs DIR writes a fixed sample of what the last timed step computed
+(dump_outputs); the inputs are counter-based, so the same arguments give the same inputs in every run.
 
 Workload ("step"): one pass of the hot path -- 2x Mitchell upscale + conv 9x9x1->64 + conv 1x1x64->32 +
 conv 5x5x32->1, strict (bit-exact) mode -- over a batch of F synthetic 3840x2160 planar-float32 Y frames
@@ -15,7 +22,7 @@ One JSON line on rank 0.  `value` = output megapixels of ALL ranks / max-over-ra
 `roofline` is for the dominant kernel (layers 1+2, k_conv12_mfma): its average launch duration is measured
 live inside the timed region with HIP events recorded on the launch stream by the library
 (srcnn_profile_*), and priced with the algorithmic FLOPs per launch.
-`cpu_baseline` = the reference's own OpenMP path (oracle/_ref, compiled from the reference sources) or the
+With --full: `cpu_baseline` = the reference's own OpenMP path (oracle/_ref, compiled from the reference sources) or the
 C restatement (oracle/) timed on this host's cores, SURVEY.md 8(d) protocol: threads = min(physical cores, 64)
 pinned with OMP_PROC_BIND=close OMP_PLACES=cores, best of 3, config #1 (ProcessSRCNN on the butterfly image) and
 config #2 (one 1080p Y frame).  At N=1 the line also carries the rest of SURVEY 8(d): the PCIe-inclusive rate
@@ -854,14 +861,55 @@ def traffic_record():
     return None, None, None
 
 
+DUMP_SEED = 0x5C0DE0D5          # fixed: the same positions in every run and every build
+DUMP_MAX_FRAMES = 8
+DUMP_SAMPLES = 1 << 20           # positions drawn per frame (duplicates dropped)
+DUMP_EDGE = 16                   # border rows / columns kept whole: the guard-band logic lives there
+
+
+def dump_outputs(outdir, d_out, frames, n_out):
+    """--dump-outputs: what the last timed step left in the caller's output buffer (frames x 4320 x 7680 float32, rank 0's),
+    reduced to at most DUMP_MAX_FRAMES x 5.5 MB so that two builds can be compared output for output:
+      out_sample.npy    (nf, k)            float32  values at k fixed positions per frame (sorted flat indices into one
+                                                    4320 x 7680 frame, drawn from DUMP_SEED; the same positions in every frame)
+      out_edge_rows.npy (nf, 2*E, 7680)    float32  the first and the last E rows of each frame
+      out_edge_cols.npy (nf, 4320, 2*E)    float32  the first and the last E columns of each frame
+    nf = all frames up to DUMP_MAX_FRAMES, beyond that a seeded choice of DUMP_MAX_FRAMES of them (sorted)."""
+    ow, oh, e = 2 * IN_W, 2 * IN_H, DUMP_EDGE
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.arange(frames) if frames <= DUMP_MAX_FRAMES else np.sort(rng.choice(frames, DUMP_MAX_FRAMES, replace=False))
+    pos = np.unique(rng.integers(0, n_out, DUMP_SAMPLES))
+    sample = np.empty((len(pick), len(pos)), np.float32)
+    rows = np.empty((len(pick), 2 * e, ow), np.float32)
+    cols = np.empty((len(pick), oh, 2 * e), np.float32)
+    for i, f in enumerate(pick):
+        frame = d_out.to_numpy(np.float32, (oh, ow), offset=int(f) * n_out * 4)
+        sample[i] = frame.reshape(-1)[pos]
+        rows[i] = np.concatenate([frame[:e], frame[-e:]])
+        cols[i] = np.concatenate([frame[:, :e], frame[:, -e:]], axis=1)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in (("out_sample", sample), ("out_edge_rows", rows), ("out_edge_cols", cols)):
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    print("bench.py: wrote frames %s of the last timed step (%d sampled positions + %d-px borders each) to %s" %
+          ([int(f) for f in pick], len(pos), e, outdir), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=4, help="4K frames per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only (no PCIe / ProcessSRCNN / tier legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can carry: at N=1 the event-timed and clock-probed "
+                         "steps, the other generator, the non-parity tiers, the PCIe-inclusive stream, ProcessSRCNN wall times, "
+                         "BASELINE configs #2-#4 and the CPU baseline; at N>1 the RCCL connectivity probe.  Off by default: a plain "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's output frames: a fixed sample, "
+                         "see dump_outputs) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the PCIe / ProcessSRCNN / tier legs")
     ap.add_argument("--tier", default="strict", choices=["strict", "fast", "fast_f16"],
                     help="numerics tier of the timed loop.  strict (default) is the only parity mode and the only "
                          "headline; the others exist so that profiles of the non-parity kernels can be collected")
@@ -878,6 +926,8 @@ def main():
     ap.add_argument("--plain-launches", action="store_true", help="host-stream: no hipGraph replay (same kernels, same overlap)")
     ap.add_argument("--dry-run", action="store_true", help="launcher/rendezvous plumbing only: no device, value = null")
     args = ap.parse_args()
+    if args.dump_outputs is not None and (args.workload != "frames" or args.dry_run):
+        ap.error("--dump-outputs writes the headline workload's outputs: it needs --workload frames and no --dry-run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: become the launcher.  Nothing in this process has touched (or will touch) the GPU.
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -945,11 +995,15 @@ def main():
     ms_per_step = reduce_max(dist, (t1 - t0) * 1e3 / args.steps)
     per_rank_ms = gather_per_rank(dist, world, (t_own - t0) * 1e3 / args.steps)
 
-    # N > 1: prove, outside the timed region, that RCCL connects all N ranks (one communicator + one barrier); the
+    # before anything else runs on d_out: the --full legs below overwrite it (other generator, other tiers)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, F, n_out)
+
+    # N > 1 (--full): prove, outside the timed region, that RCCL connects all N ranks (one communicator + one barrier); the
     # headline data path itself has no collective.  AFTER the measurement: a fabric that wedges half-way can leave
     # RCCL kernels spinning on the device, and those must not sit beside the timed steps.
     rccl_ranks, rccl_note = (None, None)
-    if world > 1:
+    if world > 1 and args.full:
         rccl_ranks, rccl_note = rccl_probe(S, dist, rank, world, ndev)
 
     if rank == 0:
@@ -1010,13 +1064,15 @@ def main():
         if world > 1:
             out["rccl_ranks"] = rccl_ranks
             out["devices_visible"] = ndev
+            if not args.full:
+                rccl_note = "RCCL connectivity is probed with --full"
             if rccl_note:
                 out["rccl_note"] = rccl_note
         if args.tier != "strict":
             out["metric"] = METRIC + " [NON-PARITY tier %s]" % args.tier
             out["roofline"]["kernel"] = {"fast": "k_conv12_mfma<fast> (fp32 MFMA FMA chains)", "fast_f16": "k_fused_f16 (all three layers, split-fp16 MFMA)"}[args.tier]
             out["roofline"]["note"] = "non-parity tier: priced with the same algorithmic FLOPs of layers 1+2 (+3 for the fused kernel: see whole_path)"
-        if world == 1 and not args.no_extras and args.tier == "strict":
+        if world == 1 and args.full and not args.no_extras and args.tier == "strict":
             # SURVEY 8d also asks for the median of >= 10 device-timed steps: 10 more steps, each bracketed by HIP events on
             # the launch stream (outside the contract's timed region, which may not contain extra synchronisation)
             evs = [S.Event() for _ in range(11)]
@@ -1070,7 +1126,7 @@ def main():
                 out["configs"] = baseline_configs(S)
             except Exception as e:                                # noqa: BLE001
                 out["configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and args.tier == "strict":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.tier == "strict":
             try:
                 out["cpu_baseline"], out["max_abs_dY_vs_cpu_ref"] = cpu_baseline(S)
             except Exception as e:                                # noqa: BLE001

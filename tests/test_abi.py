@@ -179,17 +179,11 @@ def test_output_size_matches_reference_geometry(S, golden):
         S.output_size(0, 4, 2.0)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference header not present on this machine")
-def test_program_built_against_reference_header_links_and_runs(S, tmp_path):
-    """A C++ program compiled against the REFERENCE's own libsrcnn.h (default argument, reference parameters,
-    enum) links against libsrcnn_amd.so unchanged and gets the reference's early return codes."""
-    import subprocess
-    src = tmp_path / "app.cpp"
-    src.write_text(r'''
+HEADER_APP = r"""
 #include <cstdio>
 #include "libsrcnn.h"
 int main() {
-    ConfigureFilterSRCNN(SRCNNF_Lanczos3);            // default stepscale argument from the reference header
+    ConfigureFilterSRCNN(SRCNNF_Lanczos3);            // default stepscale argument from the header
     ConfigureFilterSRCNN(SRCNNF_Bicubic, false);
     unsigned char px[4 * 4 * 3] = {0};
     unsigned char* out = nullptr; unsigned outsz = 0;
@@ -200,11 +194,61 @@ int main() {
     delete[] out;
     return 0;
 }
-''')
+"""
+# A libsrcnn.so that only logs what it is called with: the arguments the header makes HEADER_APP pass (enum values, the
+# default argument, every parameter), whatever the header's spelling of them.
+HEADER_STUB = r"""
+#include <cstdio>
+void ConfigureFilterSRCNN(SRCNNFilterType f, bool s) { std::fprintf(stderr, "configure %d %d\n", (int)f, (int)s); }
+int ProcessSRCNN(const unsigned char* p, unsigned w, unsigned h, unsigned d, float m, unsigned char*& o, unsigned& osz,
+                 unsigned char** c, unsigned* csz) {
+    std::fprintf(stderr, "process %d %u %u %u %a %d %u %d %d\n", p != nullptr, w, h, d, m, o != nullptr, osz, c != nullptr, csz != nullptr);
+    return -1;
+}
+"""
+REFERENCE_HEADER = os.path.join(ROOT, "tests", "golden", "reference_header_calls.json")
+
+
+def _header_program(incdir, workdir):
+    """HEADER_APP compiled against <incdir>/libsrcnn.h: (object, the SRCNN symbols it needs, the calls a logging stub sees)."""
+    import subprocess
+    app, stub = os.path.join(workdir, "app.cpp"), os.path.join(workdir, "stub.cpp")
+    open(app, "w").write(HEADER_APP)
+    open(stub, "w").write(HEADER_STUB)
+    obj = os.path.join(workdir, "app.o")
+    subprocess.check_call(["g++", "-std=c++11", "-c", app, "-I" + incdir, "-o", obj])
+    nm = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout.split()
+    symbols = sorted(n for n in nm if "SRCNN" in n)
+    stubdir = os.path.join(workdir, "stub")
+    os.makedirs(stubdir, exist_ok=True)
+    # the stub is compiled against the project's header: it must define exactly the symbols the program asks for
+    subprocess.check_call(["g++", "-std=c++11", "-shared", "-fPIC", stub, "-I" + os.path.join(ROOT, "include"), "-include",
+                           os.path.join(ROOT, "include", "libsrcnn_dropin.h"), "-o", os.path.join(stubdir, "libsrcnn.so")])
+    exe = os.path.join(workdir, "app_on_stub")
+    subprocess.check_call(["g++", obj, "-L" + stubdir, "-lsrcnn", "-Wl,-rpath," + stubdir, "-o", exe])
+    calls = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stderr.splitlines()
+    return obj, symbols, calls
+
+
+def test_program_built_against_reference_header_links_and_runs(S, tmp_path):
+    """A C++ program written against the reference's libsrcnn.h (default argument, reference parameters, enum), compiled
+    against the header `make install` installs as libsrcnn.h, asks for exactly the symbols and passes exactly the arguments
+    that the reference's own header makes it ask for and pass (recorded in tests/golden/reference_header_calls.json by
+    `python tests/test_abi.py --record-reference-header <dir holding the reference's libsrcnn.h>`), links against
+    libsrcnn_amd.so unchanged and gets the reference's early return codes."""
+    import json
+    import shutil
+    import subprocess
+    rec = json.load(open(REFERENCE_HEADER))
+    inc = tmp_path / "inc"
+    inc.mkdir()
+    shutil.copy(os.path.join(ROOT, "include", "libsrcnn_dropin.h"), inc / "libsrcnn.h")
+    obj, symbols, calls = _header_program(str(inc), str(tmp_path))
+    assert symbols == rec["symbols"], (symbols, rec["symbols"])
+    assert calls == rec["calls"], (calls, rec["calls"])
     exe = tmp_path / "app"
     libdir = os.path.dirname(S.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++11", str(src), "-I/root/reference/src", "-L" + libdir, "-lsrcnn_amd",
-                           "-Wl,-rpath," + libdir, "-o", str(exe)])
+    subprocess.check_call(["g++", obj, "-L" + libdir, "-lsrcnn_amd", "-Wl,-rpath," + libdir, "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120).stdout.split()
     assert out[0] == "-1" and out[1] == "-2"
     assert out[2] in ("0", "-200")
@@ -346,3 +390,17 @@ def test_switches_that_are_not_understood_are_said_once(S):
     assert "SRCNN_MAX_LANES=many is not an integer" in r.stderr
     assert "SRCNN_TEST_SEED" not in r.stderr and "SRCNN_BENCH_FAKE" not in r.stderr and "SRCNN_TRACE" not in r.stderr
     assert "SRCNN_TRACE=1 (default 0)" in r.stdout and "SRCNN_THP=0 (default 1)" in r.stdout and "SRCNN_MAX_LANES=4 (default 4)" in r.stdout
+
+
+if __name__ == "__main__":
+    import json
+    import sys
+    import tempfile
+    if len(sys.argv) != 3 or sys.argv[1] != "--record-reference-header":
+        sys.exit("usage: python tests/test_abi.py --record-reference-header <directory holding the reference's libsrcnn.h>")
+    with tempfile.TemporaryDirectory() as td:
+        _obj, symbols, calls = _header_program(os.path.abspath(sys.argv[2]), td)
+    with open(REFERENCE_HEADER, "w") as f:
+        json.dump({"symbols": symbols, "calls": calls}, f, indent=1)
+        f.write("\n")
+    print("recorded", REFERENCE_HEADER)

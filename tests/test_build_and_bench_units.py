@@ -1,9 +1,12 @@
-"""CPU: the build's staleness check is content-based, and bench.py never quotes an HBM-traffic counter that was measured
-on a different text of the dominant kernel."""
+"""CPU: the build's staleness check is content-based, bench.py never quotes an HBM-traffic counter that was measured
+on a different text of the dominant kernel, and its --dump-outputs sample is fixed and bounded."""
 import json
 import os
 import shutil
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,3 +66,61 @@ def test_kernel_source_sha_sees_the_kernel():
     assert a and len(a) == 64
     assert b.kernel_source_sha("k_conv3") not in (None, a)
     assert b.kernel_source_sha("k_does_not_exist") is None
+
+
+class _HostFrames:
+    """Stands in for the bench's device output buffer: to_numpy() of frames held in host memory."""
+    def __init__(self, frames):
+        self.data = frames
+
+    def to_numpy(self, dtype, shape, offset=0):
+        flat = self.data.reshape(-1)
+        n = int(np.prod(shape))
+        assert offset % 4 == 0 and offset // 4 + n <= flat.size
+        return flat[offset // 4: offset // 4 + n].astype(dtype).reshape(shape)
+
+
+def _frames(n):
+    import bench
+    oh, ow = 2 * bench.IN_H, 2 * bench.IN_W
+    base = np.arange(oh * ow, dtype=np.float32).reshape(oh, ow)
+    return np.stack([base + 1e6 * f for f in range(n)])
+
+
+@pytest.mark.parametrize("frames", [1, 4, 11])
+def test_dump_outputs_is_a_fixed_sample_of_every_frame_within_64mb(tmp_path, frames):
+    """--dump-outputs: the same positions in every run, values that are the frames' own, the borders whole, float32 only,
+    at most 64 MB in all."""
+    import bench
+    out = _frames(frames)
+    n_out = 4 * bench.IN_W * bench.IN_H
+    bench.dump_outputs(str(tmp_path / "a"), _HostFrames(out), frames, n_out)
+    bench.dump_outputs(str(tmp_path / "b"), _HostFrames(out), frames, n_out)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["out_edge_cols.npy", "out_edge_rows.npy", "out_sample.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / "a" / name)
+    assert total <= 64 << 20
+    sample, rows, cols = (np.load(tmp_path / "a" / n) for n in ("out_sample.npy", "out_edge_rows.npy", "out_edge_cols.npy"))
+    nf = min(frames, bench.DUMP_MAX_FRAMES)
+    assert sample.shape[0] == rows.shape[0] == cols.shape[0] == nf
+    assert sample.shape[1] > bench.DUMP_SAMPLES // 2
+    e = bench.DUMP_EDGE
+    picked = np.round(rows[:, 0, 0] / 1e6).astype(int)             # frame f holds index + 1e6 * f
+    assert len(set(picked)) == nf and all(0 <= f < frames for f in picked)
+    for i, f in enumerate(picked):
+        assert np.array_equal(rows[i], np.concatenate([out[f, :e], out[f, -e:]]))
+        assert np.array_equal(cols[i], np.concatenate([out[f, :, :e], out[f, :, -e:]], axis=1))
+        pos = (sample[i] - np.float32(1e6 * f)).astype(np.int64)
+        assert np.array_equal(out[f].reshape(-1)[pos], sample[i])
+
+
+def test_dump_outputs_is_refused_where_there_is_no_headline_output():
+    import subprocess
+    for extra in (["--dry-run"], ["--workload", "tiled8k"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "x"] + extra,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr, r.stderr

@@ -23,5 +23,5 @@ for T in strict fast_f16; do
   rocprofv3 --pmc $SQ --output-format csv -d $OUT/pmc_sq_$T -- python3 bench.py $ONE --tier $T > $OUT/bench_pmc_sq_$T.json 2> $OUT/pmc_sq_$T.err
   rocprofv3 --pmc $SQ2 --output-format csv -d $OUT/pmc_sq2_$T -- python3 bench.py $ONE --tier $T > $OUT/bench_pmc_sq2_$T.json 2> $OUT/pmc_sq2_$T.err
 done
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 find $OUT -name "*.csv" | head -40

@@ -39,8 +39,8 @@ PY
     for WL in frames tiled8k host-stream; do
         echo "== N=$N workload=$WL" >&2
         # bench.py is its own launcher: without WORLD_SIZE in the environment it starts the N ranks itself (fresh children,
-        # the parent never touches the GPU) and prints the one aggregated JSON line
-        python3 bench.py --gpus "$N" --steps 5 --warmup 2 --workload $WL --no-extras --no-cpu-baseline
+        # the parent never touches the GPU) and prints the one aggregated JSON line; --full: at N > 1 the RCCL probe (rccl_ranks)
+        python3 bench.py --gpus "$N" --steps 5 --warmup 2 --workload $WL --full --no-extras --no-cpu-baseline
     done
     echo "== N=$N workload=host-stream, plain launches (no hipGraph replay)" >&2
     python3 bench.py --gpus "$N" --steps 5 --warmup 2 --workload host-stream --plain-launches --no-extras --no-cpu-baseline
