@@ -133,9 +133,26 @@ def test_no_cpu_fallback(S):
     assert rc == -200 and out is None
 
 
-@pytest.mark.parametrize("dst,src,filt", [(16, 8, 2), (74, 37, 2), (18, 9, 2), (10, 5, 2), (2, 1, 2), (4, 2, 2),
-                                          (6, 3, 2), (46, 23, 1), (34, 23, 3), (69, 23, 4), (9, 19, 0), (11, 19, 2),
-                                          (2160, 1080, 2), (57, 19, 1)])
+def _dispatch_case_tables():
+    """(dst, src, filter) of both axes of every case of the resampler / colour-shell dispatch tests (chroma filter included)."""
+    import resample_dispatch as M
+    import test_gpu_colour_shell as SHELL
+    import test_gpu_resample_dispatch as PLANE
+    out = set()
+    for sh, sw, dh, dw in PLANE.PLANE_CASES + PLANE.TALL_CASES:
+        out |= {(dw, sw, f) for f in M.FILTERS} | {(dh, sh, f) for f in M.FILTERS}
+    for h, w, d, f, mul in SHELL.CASES + [SHELL.LARGE_CASE]:
+        dw, dh = M.out_size(w, h, mul)
+        out |= {(dw, w, g) for g in (f, M.chroma_filter(f))} | {(dh, h, g) for g in (f, M.chroma_filter(f))}
+    return sorted(out)
+
+
+AXIS_TABLE_CASES = [(16, 8, 2), (74, 37, 2), (18, 9, 2), (10, 5, 2), (2, 1, 2), (4, 2, 2), (6, 3, 2), (46, 23, 1), (34, 23, 3),
+                    (69, 23, 4), (9, 19, 0), (11, 19, 2), (2160, 1080, 2), (57, 19, 1)]
+
+
+# (the dispatch tables that repeat a case above are left out: a repeated parameter set would rename both test ids)
+@pytest.mark.parametrize("dst,src,filt", AXIS_TABLE_CASES + [t for t in _dispatch_case_tables() if t not in AXIS_TABLE_CASES])
 def test_axis_table_matches_oracle(S, oracle_lib, dst, src, filt):
     a = S.axis_table(dst, src, filt)
     b = oracle_lib.axis_table(dst, src, filt)
