@@ -47,7 +47,9 @@ DEBUG_SYMBOLS = [
     "srcnn_set_relaxation", "srcnn_axis_table", "srcnn_fused_diag", "srcnn_debug_counts", "srcnn_debug_settings",
     "srcnn_debug_clock_probe", "srcnn_debug_clock_read", "srcnn_debug_band_plan", "srcnn_debug_process_phases", "srcnn_debug_stream_mode",
 ]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS          # everything the library exports besides the two C++ symbols
+# the YUV 4:2:0 extension (include/srcnn_amd_yuv.h, listed in include/srcnn_amd_yuv.abi; versioned on its own)
+YUV_SYMBOLS = ["srcnn_yuv_abi_version", "srcnn_yuv420_upscale_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -122,10 +124,12 @@ def lib():
             "srcnn_debug_process_phases": (i, [C.POINTER(C.c_double), i]),
             "srcnn_debug_stream_mode": (i, [C.POINTER(u), C.POINTER(u), C.POINTER(i)]),
             "srcnn_comm_barrier": (i, [vp]), "srcnn_comm_wait": (i, [vp]), "srcnn_comm_set_timeout_ms": (i, [i]),
+            "srcnn_yuv_abi_version": (i, []),
+            "srcnn_yuv420_upscale_dev": (i, [i, u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
-                continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer instruments
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+                continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         cfg = getattr(L, CXX_SYMBOLS[0])
@@ -450,6 +454,66 @@ def process_u8(rgb, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=True):
     check(lib().srcnn_process_u8(rgb.ctypes.data, w, h, d, float(m), filt, out.ctypes.data,
                                  conv.ctypes.data if want_conv else None))
     return out, conv
+
+
+YUV_I420, YUV_NV12 = 0, 1
+_YUV_FORMATS = {"i420": YUV_I420, "nv12": YUV_NV12, YUV_I420: YUV_I420, YUV_NV12: YUV_NV12}
+
+
+def yuv420_sizes(w, h, multiply):
+    """((dw, dh), (cw, ch), (dcw, dch)): luma output and chroma input / output sizes of srcnn_yuv420_upscale_dev."""
+    dw, dh = output_size(w, h, multiply)
+    return (dw, dh), ((w + 1) // 2, (h + 1) // 2), ((dw + 1) // 2, (dh + 1) // 2)
+
+
+def _addr(p):
+    """A plane argument of yuv420_upscale_dev: None, an address, a DeviceBuffer, or (DeviceBuffer | address, byte offset)."""
+    if p is None:
+        return None
+    if isinstance(p, tuple):
+        base, off = p
+        return _addr(base) + int(off)
+    return p.ptr if isinstance(p, DeviceBuffer) else int(p)
+
+
+def yuv420_upscale_dev(fmt, w, h, multiply, filt, src, src_pitch, dst, dst_pitch, stream=None):
+    """srcnn_yuv420_upscale_dev on device memory, as given: src / dst are 3 plane arguments (see _addr; NV12 ignores the
+    third), pitches 3 byte counts (0 = tight) or None.  Asynchronous on `stream` (a Stream, a raw handle or None);
+    raises SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    s = (vp * 3)(*[_addr(p) for p in src])
+    d = (vp * 3)(*[_addr(p) for p in dst])
+    sp = (sz * 3)(*src_pitch) if src_pitch is not None else None
+    dp = (sz * 3)(*dst_pitch) if dst_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_yuv420_upscale_dev(int(_YUV_FORMATS.get(fmt, fmt)), int(w), int(h), float(np.float32(multiply)), int(filt), s, sp,
+                                         d, dp, handle))
+
+
+def yuv420_upscale(y, u, v=None, multiply=2.0, filt=SRCNNF_Bicubic, fmt="i420", stream=None):
+    """One 8-bit YUV 4:2:0 frame through srcnn_yuv420_upscale_dev: numpy u8 planes in, numpy u8 planes out.
+    I420: y (h, w), u and v (ceil(h/2), ceil(w/2)) -> (y', u', v').  NV12: y, and u = the interleaved UV plane
+    (ceil(h/2), 2 ceil(w/2)) or (ceil(h/2), ceil(w/2), 2); v unused -> (y', uv') with uv' (ceil(dh/2), 2 ceil(dw/2))."""
+    fmt = _YUV_FORMATS[fmt.lower() if isinstance(fmt, str) else fmt]
+    y = np.ascontiguousarray(y, np.uint8)
+    h, w = y.shape
+    (dw, dh), (cw, ch), (dcw, dch) = yuv420_sizes(w, h, multiply)
+    if fmt == YUV_NV12:
+        planes = [y, np.ascontiguousarray(u, np.uint8).reshape(ch, 2 * cw)]
+        shapes = [(dh, dw), (dch, 2 * dcw)]
+    else:
+        planes = [y, np.ascontiguousarray(u, np.uint8), np.ascontiguousarray(v, np.uint8)]
+        assert planes[1].shape == planes[2].shape == (ch, cw), (planes[1].shape, planes[2].shape, (ch, cw))
+        shapes = [(dh, dw), (dch, dcw), (dch, dcw)]
+    din = [DeviceBuffer.from_numpy(p) for p in planes]
+    dout = [DeviceBuffer(int(np.prod(s))) for s in shapes]
+    pad = [None] * (3 - len(planes))
+    yuv420_upscale_dev(fmt, w, h, multiply, filt, din + pad, None, dout + pad, None, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    return tuple(b.to_numpy(np.uint8, s) for b, s in zip(dout, shapes))
 
 
 class PinnedArray:

@@ -12,9 +12,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsrcnn_amd.so")
 
-SOURCES = ["srcnn_kernels.hip", "srcnn_fused_f16.hip", "srcnn_capi.cpp", "srcnn_pipeline.cpp", "srcnn_comm.cpp", "dropin.cpp"]
-DEPS = SOURCES + ["../../tools/srcnntest.cpp", "srcnn_kernels.h", "srcnn_host.hpp", "srcnn_settings.hpp", "srcnn_watchdog.hpp", "resample_table.hpp", "srcnn_weights.inc",
-                  "../../include/srcnn_amd.h", "../../include/srcnn_amd_debug.h", "../../include/libsrcnn_dropin.h", "exports.map"]
+SOURCES = ["srcnn_kernels.hip", "srcnn_fused_f16.hip", "srcnn_yuv.hip", "srcnn_capi.cpp", "srcnn_pipeline.cpp", "srcnn_comm.cpp", "dropin.cpp"]
+DEPS = SOURCES + ["../../tools/srcnntest.cpp", "../../tools/srcnnyuv.cpp", "srcnn_kernels.h", "srcnn_yuv.h", "srcnn_host.hpp", "srcnn_settings.hpp", "srcnn_watchdog.hpp", "resample_table.hpp", "srcnn_weights.inc",
+                  "../../include/srcnn_amd.h", "../../include/srcnn_amd_debug.h", "../../include/srcnn_amd_yuv.h",
+                  "../../include/libsrcnn_dropin.h", "exports.map"]
 
 # -ffp-contract=off: strict kernels and the host table builder must round every multiply and add
 # separately (the reference binary contains no FMA).  FAST kernels call fmaf explicitly.
@@ -171,18 +172,20 @@ def build(force=False, verbose=True):
 
 
 def build_cli(verbose=True):
-    """tools/srcnntest.cpp -> libsrcnn_amd/bin/srcnntest: the counterpart of the reference's CLI harness,
-    linked against the drop-in library exactly as a libsrcnn user would link."""
+    """tools/srcnntest.cpp -> libsrcnn_amd/bin/srcnntest: the counterpart of the reference's CLI harness, and
+    tools/srcnnyuv.cpp -> libsrcnn_amd/bin/srcnnyuv (YUV4MPEG2 streams through the YUV 4:2:0 call), both linked against the
+    library exactly as a libsrcnn user would link."""
     root = os.path.dirname(HERE)
     bindir = os.path.join(HERE, "bin")
     os.makedirs(bindir, exist_ok=True)
-    exe = os.path.join(bindir, "srcnntest")
-    cmd = ["g++", "-O2", "-std=c++17", os.path.join(root, "tools", "srcnntest.cpp"), "-L" + LIBDIR, "-lsrcnn_amd",
-           "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,$ORIGIN/../lib", "-o", exe]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return exe
+    for name in ("srcnntest", "srcnnyuv"):
+        exe = os.path.join(bindir, name)
+        cmd = ["g++", "-O2", "-std=c++17", os.path.join(root, "tools", name + ".cpp"), "-L" + LIBDIR, "-lsrcnn_amd",
+               "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,$ORIGIN/../lib", "-o", exe]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return os.path.join(bindir, "srcnntest")
 
 
 if __name__ == "__main__":

@@ -26,6 +26,8 @@
 #include <unistd.h>
 
 #include "srcnn_host.hpp"
+#include "srcnn_yuv.h"
+#include "../../include/srcnn_amd_yuv.h"
 
 namespace srcnn {
 
@@ -1166,6 +1168,105 @@ void release_context(Ctx& cx)
     { std::lock_guard<std::mutex> hl(cx.host_call.mu); cx.host_call.release(); }
 }
 
+// ---- 8-bit YUV 4:2:0 frames (include/srcnn_amd_yuv.h) ----
+
+struct YuvPlane {
+    const unsigned char* lo = nullptr;   // first byte of the plane
+    size_t pitch = 0, row_bytes = 0;
+    unsigned rows = 0;
+    const unsigned char* hi() const { return lo + pitch * (rows - 1) + row_bytes; }   // one past the last byte
+};
+
+bool overlaps(const YuvPlane& a, const YuvPlane& b) { return a.lo < b.hi() && b.lo < a.hi(); }
+
+// Everything srcnn_yuv420_upscale_dev refuses, checked before any device lookup.
+int check_yuv_args(int format, unsigned w, unsigned h, float multiply, int filter, const unsigned char* const src[3],
+                   const size_t src_pitch[3], unsigned char* const dst[3], const size_t dst_pitch[3], unsigned& dw,
+                   unsigned& dh, YuvPlane in[3], YuvPlane out[3])
+{
+    if (format != SRCNN_YUV_I420 && format != SRCNN_YUV_NV12) return fail(SRCNN_E_ARG, "unknown YUV format %d", format);
+    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    const int np = format == SRCNN_YUV_NV12 ? 2 : 3;
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
+    for (int k = 0; k < np; ++k)
+        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
+    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
+    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
+    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
+        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
+    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
+    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
+        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
+    const unsigned cw = (w + 1) / 2, ch = (h + 1) / 2, dcw = (dw + 1) / 2, dch = (dh + 1) / 2;
+    for (int side = 0; side < 2; ++side) {
+        YuvPlane* P = side ? out : in;
+        const unsigned pw = side ? dw : w, ph = side ? dh : h, pcw = side ? dcw : cw, pch = side ? dch : ch;
+        const size_t* pitch = side ? dst_pitch : src_pitch;
+        for (int k = 0; k < np; ++k) {
+            YuvPlane& p = P[k];
+            p.lo = side ? dst[k] : src[k];
+            p.row_bytes = k == 0 ? pw : (np == 2 ? 2 * (size_t)pcw : pcw);
+            p.rows = k == 0 ? ph : pch;
+            p.pitch = pitch && pitch[k] ? pitch[k] : p.row_bytes;
+            if (p.pitch < p.row_bytes)
+                return fail(SRCNN_E_ARG, "%s pitch %zu of plane %d is below its row of %zu bytes", side ? "output" : "input", p.pitch, k, p.row_bytes);
+        }
+    }
+    for (int a = 0; a < np; ++a)
+        for (int b = 0; b < np; ++b)
+            if (overlaps(in[a], out[b])) return fail(SRCNN_E_ARG, "input plane %d overlaps output plane %d", a, b);
+    return SRCNN_OK;
+}
+
+// Rows of Y' one pass of the Y path produces: the whole frame when its layer-2 planes fit the workspace cap (y_path_range's
+// test), else budget_band_rows.
+unsigned yuv_band_rows(const Call& c, unsigned dw, unsigned dh)
+{
+    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
+    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)dh + 4) <= G.ws_budget.load()) return dh;
+    return std::min(dh, budget_band_rows(dw));
+}
+
+// unpack -> chroma resample + pack -> Y' band by band (Y path into a float band, pack into the destination rows)
+int yuv420_frame(Call& c, bool nv12, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
+                 const YuvPlane out[3])
+{
+    Workspace& ws = *c.ws;
+    const unsigned cw = (w + 1) / 2, ch = (h + 1) / 2, dcw = (dw + 1) / 2, dch = (dh + 1) / 2;
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels)
+    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t o_u = up64((size_t)w * h), o_v = o_u + up64((size_t)cw * ch), o_cu = o_v + up64((size_t)cw * ch);
+    const size_t o_cv = o_cu + up64((size_t)dcw * dch), o_y = o_cv + up64((size_t)dcw * dch), total = o_y + (size_t)dw * band;
+    int rc;
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, total))) return rc;
+    float* P = ws.planes;
+    launch_yuv_unpack(in[0].lo, in[0].pitch, w, h, false, P, nullptr, c.s);
+    if (nv12) launch_yuv_unpack(in[1].lo, in[1].pitch, cw, ch, true, P + o_u, P + o_v, c.s);
+    else {
+        launch_yuv_unpack(in[1].lo, in[1].pitch, cw, ch, false, P + o_u, nullptr, c.s);
+        launch_yuv_unpack(in[2].lo, in[2].pitch, cw, ch, false, P + o_v, nullptr, c.s);
+    }
+    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
+    if ((rc = resample_rows_range(c, P + o_u, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cu))) return rc;
+    if ((rc = resample_rows_range(c, P + o_v, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cv))) return rc;
+    unsigned char* const du = const_cast<unsigned char*>(out[1].lo);
+    if (nv12) launch_yuv_pack(P + o_cu, P + o_cv, dcw, dch, true, du, out[1].pitch, 0, c.s);
+    else {
+        launch_yuv_pack(P + o_cu, nullptr, dcw, dch, true, du, out[1].pitch, 0, c.s);
+        launch_yuv_pack(P + o_cv, nullptr, dcw, dch, true, const_cast<unsigned char*>(out[2].lo), out[2].pitch, 0, c.s);
+    }
+    const YSource ysrc = YSource::from_plane(P);
+    for (unsigned a = 0; a < dh; a += band) {
+        const unsigned b = std::min(dh, a + band);
+        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, P + o_y))) return rc;
+        launch_yuv_pack(P + o_y, nullptr, dw, b - a, false, const_cast<unsigned char*>(out[0].lo), out[0].pitch, a, c.s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 }  // namespace
 }  // namespace srcnn
 
@@ -1741,6 +1842,23 @@ int srcnn_debug_counts(int* tables, int* lanes)
     if (tables) *tables = nt;
     if (lanes) *lanes = nl;
     return SRCNN_OK;
+}
+
+// ---- 8-bit YUV 4:2:0 frames (include/srcnn_amd_yuv.h) ----
+int srcnn_yuv_abi_version(void) { return SRCNN_AMD_YUV_VERSION; }
+
+int srcnn_yuv420_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter,
+                             const unsigned char* const src[3], const size_t src_pitch[3],
+                             unsigned char* const dst[3], const size_t dst_pitch[3], void* stream)
+{
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[3], out[3];
+    int rc;
+    if ((rc = check_yuv_args(format, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv420 %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv420_frame(sc.c, format == SRCNN_YUV_NV12, w, h, dw, dh, filter, in, out);
 }
 
 }  // extern "C"
