@@ -49,8 +49,15 @@ DEBUG_SYMBOLS = [
 ]
 # the YUV 4:2:0 extension (include/srcnn_amd_yuv.h, listed in include/srcnn_amd_yuv.abi; versioned on its own)
 YUV_SYMBOLS = ["srcnn_yuv_abi_version", "srcnn_yuv420_upscale_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS   # everything the library exports besides the two C++ symbols
+# the high-bit-depth / 4:2:2 / 4:4:4 YUV extension (include/srcnn_amd_yuv_ex.h, listed in include/srcnn_amd_yuv_ex.abi; its own version)
+YUV_EX_SYMBOLS = ["srcnn_yuv_ex_abi_version", "srcnn_yuv_plane_size", "srcnn_yuv_upscale_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
+
+
+class YuvFormat(C.Structure):
+    """srcnn_yuv_format (include/srcnn_amd_yuv_ex.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("layout", C.c_int), ("chroma", C.c_int), ("depth", C.c_int), ("msb_aligned", C.c_int)]
 
 
 class SrcnnError(RuntimeError):
@@ -126,9 +133,12 @@ def lib():
             "srcnn_comm_barrier": (i, [vp]), "srcnn_comm_wait": (i, [vp]), "srcnn_comm_set_timeout_ms": (i, [i]),
             "srcnn_yuv_abi_version": (i, []),
             "srcnn_yuv420_upscale_dev": (i, [i, u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp]),
+            "srcnn_yuv_ex_abi_version": (i, []),
+            "srcnn_yuv_plane_size": (i, [C.POINTER(YuvFormat), u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(sz)]),
+            "srcnn_yuv_upscale_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -514,6 +524,74 @@ def yuv420_upscale(y, u, v=None, multiply=2.0, filt=SRCNNF_Bicubic, fmt="i420", 
     else:
         check(lib().srcnn_stream_sync(stream))
     return tuple(b.to_numpy(np.uint8, s) for b, s in zip(dout, shapes))
+
+
+YUV_PLANAR, YUV_SEMIPLANAR = 0, 1
+YUV_420, YUV_422, YUV_444 = 0, 1, 2
+_YUV_LAYOUTS = {"planar": YUV_PLANAR, "semiplanar": YUV_SEMIPLANAR, YUV_PLANAR: YUV_PLANAR, YUV_SEMIPLANAR: YUV_SEMIPLANAR}
+_YUV_CHROMAS = {"420": YUV_420, "422": YUV_422, "444": YUV_444, 420: YUV_420, 422: YUV_422, 444: YUV_444,
+                YUV_420: YUV_420, YUV_422: YUV_422, YUV_444: YUV_444}
+
+
+def yuv_format(layout="planar", chroma="420", depth=8, msb_aligned=False):
+    """A srcnn_yuv_format: layout "planar" | "semiplanar", chroma "420" | "422" | "444" (or the SRCNN_YUV_* values), depth
+    8 / 10 / 12 / 14 / 16, msb_aligned for P010-style words.  Unknown values are passed on for the library to refuse."""
+    layout = layout.lower() if isinstance(layout, str) else layout
+    return YuvFormat(C.sizeof(YuvFormat), int(_YUV_LAYOUTS.get(layout, layout)), int(_YUV_CHROMAS.get(chroma, chroma)), int(depth),
+                     int(msb_aligned))
+
+
+def yuv_plane_size(fmt, w, h, plane):
+    """(cols, rows, row_bytes) of one plane of a w x h frame (srcnn_yuv_plane_size; no device)."""
+    c, r, b = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
+    check(lib().srcnn_yuv_plane_size(C.byref(fmt), int(w), int(h), int(plane), C.byref(c), C.byref(r), C.byref(b)))
+    return c.value, r.value, b.value
+
+
+def yuv_plane_sizes(fmt, w, h, multiply):
+    """((dw, dh), src_planes, dst_planes): the output size and, per plane of the format (2 for semi-planar, else 3),
+    (cols, rows, row_bytes) of the input and of the output frame of srcnn_yuv_upscale_dev."""
+    dw, dh = output_size(w, h, multiply)
+    n = 2 if fmt.layout == YUV_SEMIPLANAR else 3
+    return ((dw, dh), [yuv_plane_size(fmt, w, h, k) for k in range(n)], [yuv_plane_size(fmt, dw, dh, k) for k in range(n)])
+
+
+def yuv_upscale_dev(fmt, w, h, multiply, filt, src, src_pitch, dst, dst_pitch, stream=None):
+    """srcnn_yuv_upscale_dev on device memory, as given: fmt a YuvFormat (yuv_format(...)) or None, src / dst 3 plane
+    arguments (see _addr; semi-planar ignores the third), pitches 3 byte counts (0 = tight) or None.  Asynchronous on
+    `stream` (a Stream, a raw handle or None); raises SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    s = (vp * 3)(*[_addr(p) for p in src]) if src is not None else None
+    d = (vp * 3)(*[_addr(p) for p in dst]) if dst is not None else None
+    sp = (sz * 3)(*src_pitch) if src_pitch is not None else None
+    dp = (sz * 3)(*dst_pitch) if dst_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_yuv_upscale_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)),
+                                      int(filt), s, sp, d, dp, handle))
+
+
+def yuv_upscale(planes, layout="planar", chroma="420", depth=8, msb_aligned=False, multiply=2.0, filt=SRCNNF_Bicubic, stream=None):
+    """One YUV frame through srcnn_yuv_upscale_dev: numpy planes in, numpy planes out, uint8 at depth 8 and uint16 above.
+    planar: (y, u, v) -> (y', u', v'); semi-planar: (y, uv) with uv (rows, 2 * cols) or (rows, cols, 2) -> (y', uv') with
+    uv' (rows, 2 * cols)."""
+    fmt = yuv_format(layout, chroma, depth, msb_aligned)
+    dt = np.uint8 if depth == 8 else np.uint16
+    y = np.ascontiguousarray(planes[0], dt)
+    h, w = y.shape
+    _, src_sizes, dst_sizes = yuv_plane_sizes(fmt, w, h, multiply)
+    bps = np.dtype(dt).itemsize
+    ins = [y] + [np.ascontiguousarray(p, dt).reshape(r, rb // bps) for p, (_c, r, rb) in zip(planes[1:], src_sizes[1:])]
+    assert len(ins) == len(src_sizes), "%d planes given, the format has %d" % (len(ins), len(src_sizes))
+    shapes = [(r, rb // bps) for (_c, r, rb) in dst_sizes]
+    din = [DeviceBuffer.from_numpy(p) for p in ins]
+    dout = [DeviceBuffer(max(1, int(np.prod(s)) * bps)) for s in shapes]
+    pad = [None] * (3 - len(ins))
+    yuv_upscale_dev(fmt, w, h, multiply, filt, din + pad, None, dout + pad, None, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    return tuple(b.to_numpy(dt, s) for b, s in zip(dout, shapes))
 
 
 class PinnedArray:

@@ -28,6 +28,7 @@
 #include "srcnn_host.hpp"
 #include "srcnn_yuv.h"
 #include "../../include/srcnn_amd_yuv.h"
+#include "../../include/srcnn_amd_yuv_ex.h"
 
 namespace srcnn {
 
@@ -1168,7 +1169,7 @@ void release_context(Ctx& cx)
     { std::lock_guard<std::mutex> hl(cx.host_call.mu); cx.host_call.release(); }
 }
 
-// ---- 8-bit YUV 4:2:0 frames (include/srcnn_amd_yuv.h) ----
+// ---- YUV frames (include/srcnn_amd_yuv.h: 8-bit 4:2:0; include/srcnn_amd_yuv_ex.h: every other format) ----
 
 struct YuvPlane {
     const unsigned char* lo = nullptr;   // first byte of the plane
@@ -1179,15 +1180,47 @@ struct YuvPlane {
 
 bool overlaps(const YuvPlane& a, const YuvPlane& b) { return a.lo < b.hi() && b.lo < a.hi(); }
 
-// Everything srcnn_yuv420_upscale_dev refuses, checked before any device lookup.
-int check_yuv_args(int format, unsigned w, unsigned h, float multiply, int filter, const unsigned char* const src[3],
-                   const size_t src_pitch[3], unsigned char* const dst[3], const size_t dst_pitch[3], unsigned& dw,
+// What a frame format comes down to for the frame function: plane count, chroma subsampling, sample width, read / write rule.
+struct YuvGeom {
+    bool semi = false;       // Y + interleaved UV (2 planes) instead of Y, U, V
+    unsigned sx = 1, sy = 1; // chroma columns = ceil(w / 2^sx), rows = ceil(h / 2^sy)
+    unsigned bps = 1;        // bytes per sample: 1 (depth 8) or 2
+    Yuv16Rule rule;          // bps == 2
+    unsigned ccols(unsigned w) const { return (w + sx) >> sx; }
+    unsigned crows(unsigned h) const { return (h + sy) >> sy; }
+};
+
+// srcnn_yuv_format -> YuvGeom, or SRCNN_E_ARG
+int yuv_geom_from_format(const srcnn_yuv_format* f, YuvGeom& g)
+{
+    if (!f) return fail(SRCNN_E_ARG, "NULL format");
+    if (f->struct_size != sizeof(srcnn_yuv_format)) return fail(SRCNN_E_ARG, "struct_size %u is not %zu", f->struct_size, sizeof(srcnn_yuv_format));
+    if (f->layout != SRCNN_YUV_PLANAR && f->layout != SRCNN_YUV_SEMIPLANAR) return fail(SRCNN_E_ARG, "unknown YUV layout %d", f->layout);
+    if (f->chroma != SRCNN_YUV_420 && f->chroma != SRCNN_YUV_422 && f->chroma != SRCNN_YUV_444) return fail(SRCNN_E_ARG, "unknown chroma format %d", f->chroma);
+    if (f->depth != 8 && f->depth != 10 && f->depth != 12 && f->depth != 14 && f->depth != 16) return fail(SRCNN_E_ARG, "unsupported depth %d", f->depth);
+    if ((f->msb_aligned != 0 && f->msb_aligned != 1) || (f->depth == 8 && f->msb_aligned)) return fail(SRCNN_E_ARG, "bad msb_aligned %d at depth %d", f->msb_aligned, f->depth);
+    g.semi = f->layout == SRCNN_YUV_SEMIPLANAR;
+    g.sx = f->chroma == SRCNN_YUV_444 ? 0 : 1;
+    g.sy = f->chroma == SRCNN_YUV_420 ? 1 : 0;
+    g.bps = f->depth == 8 ? 1 : 2;
+    if (g.bps == 2) {
+        const unsigned s = (unsigned)f->depth - 8, shift = f->msb_aligned ? 16u - (unsigned)f->depth : 0u;
+        g.rule.rshift = g.rule.lshift = shift;
+        g.rule.mask = (1u << f->depth) - 1u;
+        g.rule.up = (float)(1u << s);
+        g.rule.down = 1.f / g.rule.up;
+    }
+    return SRCNN_OK;
+}
+
+// Everything the YUV frame calls refuse beyond the format itself, checked before any device lookup.
+int check_yuv_args(const YuvGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[3],
+                   const size_t src_pitch[3], void* const dst[3], const size_t dst_pitch[3], unsigned& dw,
                    unsigned& dh, YuvPlane in[3], YuvPlane out[3])
 {
-    if (format != SRCNN_YUV_I420 && format != SRCNN_YUV_NV12) return fail(SRCNN_E_ARG, "unknown YUV format %d", format);
     if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
     if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    const int np = format == SRCNN_YUV_NV12 ? 2 : 3;
+    const int np = g.semi ? 2 : 3;
     if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
     for (int k = 0; k < np; ++k)
         if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
@@ -1198,19 +1231,20 @@ int check_yuv_args(int format, unsigned w, unsigned h, float multiply, int filte
     if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
     if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
         return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
-    const unsigned cw = (w + 1) / 2, ch = (h + 1) / 2, dcw = (dw + 1) / 2, dch = (dh + 1) / 2;
     for (int side = 0; side < 2; ++side) {
         YuvPlane* P = side ? out : in;
-        const unsigned pw = side ? dw : w, ph = side ? dh : h, pcw = side ? dcw : cw, pch = side ? dch : ch;
+        const unsigned pw = side ? dw : w, ph = side ? dh : h, pcw = g.ccols(pw), pch = g.crows(ph);
         const size_t* pitch = side ? dst_pitch : src_pitch;
         for (int k = 0; k < np; ++k) {
             YuvPlane& p = P[k];
-            p.lo = side ? dst[k] : src[k];
-            p.row_bytes = k == 0 ? pw : (np == 2 ? 2 * (size_t)pcw : pcw);
+            p.lo = static_cast<const unsigned char*>(side ? dst[k] : src[k]);
+            p.row_bytes = (size_t)g.bps * (k == 0 ? pw : (g.semi ? 2 * (size_t)pcw : pcw));
             p.rows = k == 0 ? ph : pch;
             p.pitch = pitch && pitch[k] ? pitch[k] : p.row_bytes;
             if (p.pitch < p.row_bytes)
                 return fail(SRCNN_E_ARG, "%s pitch %zu of plane %d is below its row of %zu bytes", side ? "output" : "input", p.pitch, k, p.row_bytes);
+            if (g.bps == 2 && ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & 1))
+                return fail(SRCNN_E_ARG, "%s plane %d: 16-bit samples need an even base address and pitch", side ? "output" : "input", k);
         }
     }
     for (int a = 0; a < np; ++a)
@@ -1228,12 +1262,13 @@ unsigned yuv_band_rows(const Call& c, unsigned dw, unsigned dh)
     return std::min(dh, budget_band_rows(dw));
 }
 
-// unpack -> chroma resample + pack -> Y' band by band (Y path into a float band, pack into the destination rows)
-int yuv420_frame(Call& c, bool nv12, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
-                 const YuvPlane out[3])
+// unpack -> chroma resample + pack -> Y' band by band (Y path into a float band, pack into the destination rows).  Depth 8
+// goes through k_yuv_unpack / k_yuv_pack, 16-bit words through k_yuv16_unpack / k_yuv16_pack.
+int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
+              const YuvPlane out[3])
 {
     Workspace& ws = *c.ws;
-    const unsigned cw = (w + 1) / 2, ch = (h + 1) / 2, dcw = (dw + 1) / 2, dch = (dh + 1) / 2;
+    const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
     const unsigned band = yuv_band_rows(c, dw, dh);
     // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels)
     auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
@@ -1242,26 +1277,34 @@ int yuv420_frame(Call& c, bool nv12, unsigned w, unsigned h, unsigned dw, unsign
     int rc;
     if ((rc = grow_ws(ws, ws.planes, ws.planes_n, total))) return rc;
     float* P = ws.planes;
-    launch_yuv_unpack(in[0].lo, in[0].pitch, w, h, false, P, nullptr, c.s);
-    if (nv12) launch_yuv_unpack(in[1].lo, in[1].pitch, cw, ch, true, P + o_u, P + o_v, c.s);
+    auto unpack = [&](const YuvPlane& p, unsigned pw, unsigned ph, bool uv, bool luma, float* d0, float* d1) {
+        if (g.bps == 1) launch_yuv_unpack(p.lo, p.pitch, pw, ph, uv, d0, d1, c.s);
+        else launch_yuv16_unpack(p.lo, p.pitch, pw, ph, uv, g.rule, luma, d0, d1, c.s);
+    };
+    auto pack = [&](const float* s0, const float* s1, unsigned pw, unsigned ph, bool sat, const YuvPlane& p, unsigned row0) {
+        unsigned char* d = const_cast<unsigned char*>(p.lo);
+        if (g.bps == 1) launch_yuv_pack(s0, s1, pw, ph, sat, d, p.pitch, row0, c.s);
+        else launch_yuv16_pack(s0, s1, pw, ph, sat, g.rule, d, p.pitch, row0, c.s);
+    };
+    unpack(in[0], w, h, false, true, P, nullptr);
+    if (g.semi) unpack(in[1], cw, ch, true, false, P + o_u, P + o_v);
     else {
-        launch_yuv_unpack(in[1].lo, in[1].pitch, cw, ch, false, P + o_u, nullptr, c.s);
-        launch_yuv_unpack(in[2].lo, in[2].pitch, cw, ch, false, P + o_v, nullptr, c.s);
+        unpack(in[1], cw, ch, false, false, P + o_u, nullptr);
+        unpack(in[2], cw, ch, false, false, P + o_v, nullptr);
     }
     const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
     if ((rc = resample_rows_range(c, P + o_u, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cu))) return rc;
     if ((rc = resample_rows_range(c, P + o_v, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cv))) return rc;
-    unsigned char* const du = const_cast<unsigned char*>(out[1].lo);
-    if (nv12) launch_yuv_pack(P + o_cu, P + o_cv, dcw, dch, true, du, out[1].pitch, 0, c.s);
+    if (g.semi) pack(P + o_cu, P + o_cv, dcw, dch, true, out[1], 0);
     else {
-        launch_yuv_pack(P + o_cu, nullptr, dcw, dch, true, du, out[1].pitch, 0, c.s);
-        launch_yuv_pack(P + o_cv, nullptr, dcw, dch, true, const_cast<unsigned char*>(out[2].lo), out[2].pitch, 0, c.s);
+        pack(P + o_cu, nullptr, dcw, dch, true, out[1], 0);
+        pack(P + o_cv, nullptr, dcw, dch, true, out[2], 0);
     }
     const YSource ysrc = YSource::from_plane(P);
     for (unsigned a = 0; a < dh; a += band) {
         const unsigned b = std::min(dh, a + band);
         if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, P + o_y))) return rc;
-        launch_yuv_pack(P + o_y, nullptr, dw, b - a, false, const_cast<unsigned char*>(out[0].lo), out[0].pitch, a, c.s);
+        pack(P + o_y, nullptr, dw, b - a, false, out[0], a);
     }
     HIP_TRY(hipGetLastError());
     return SRCNN_OK;
@@ -1851,14 +1894,58 @@ int srcnn_yuv420_upscale_dev(int format, unsigned w, unsigned h, float multiply,
                              const unsigned char* const src[3], const size_t src_pitch[3],
                              unsigned char* const dst[3], const size_t dst_pitch[3], void* stream)
 {
+    if (format != SRCNN_YUV_I420 && format != SRCNN_YUV_NV12) return fail(SRCNN_E_ARG, "unknown YUV format %d", format);
+    YuvGeom g;                              // 8-bit 4:2:0
+    g.semi = format == SRCNN_YUV_NV12;
     unsigned dw = 0, dh = 0;
     YuvPlane in[3], out[3];
     int rc;
-    if ((rc = check_yuv_args(format, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    if ((rc = check_yuv_args(g, w, h, multiply, filter, reinterpret_cast<const void* const*>(src), src_pitch,
+                             reinterpret_cast<void* const*>(dst), dst_pitch, dw, dh, in, out))) return rc;
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
     TraceRange tr("srcnn yuv420 %ux%u -> %ux%u", w, h, dw, dh);
-    return yuv420_frame(sc.c, format == SRCNN_YUV_NV12, w, h, dw, dh, filter, in, out);
+    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- YUV frames of any supported depth / chroma format (include/srcnn_amd_yuv_ex.h) ----
+int srcnn_yuv_ex_abi_version(void) { return SRCNN_AMD_YUV_EX_VERSION; }
+
+int srcnn_yuv_plane_size(const srcnn_yuv_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
+                         size_t* row_bytes)
+{
+    YuvGeom g;
+    int rc;
+    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    if (plane < 0 || plane > 2) return fail(SRCNN_E_ARG, "plane %d", plane);
+    unsigned pc = w, pr = h;
+    size_t rb = (size_t)g.bps * w;
+    if (plane > 0) {
+        pc = g.ccols(w), pr = g.crows(h);
+        rb = (size_t)g.bps * pc * (g.semi ? 2 : 1);
+        if (g.semi && plane == 2) pc = pr = 0, rb = 0;
+    }
+    if (cols) *cols = pc;
+    if (rows) *rows = pr;
+    if (row_bytes) *row_bytes = rb;
+    return SRCNN_OK;
+}
+
+int srcnn_yuv_upscale_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                          const void* const src[3], const size_t src_pitch[3],
+                          void* const dst[3], const size_t dst_pitch[3], void* stream)
+{
+    YuvGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[3], out[3];
+    int rc;
+    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
+    if ((rc = check_yuv_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
 }
 
 }  // extern "C"

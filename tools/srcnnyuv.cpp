@@ -1,12 +1,14 @@
-// srcnnyuv -- YUV4MPEG2 (.y4m) video through srcnn_yuv420_upscale_dev (include/srcnn_amd_yuv.h): every frame's Y plane goes
-// through SRCNN with the chosen filter, its chroma planes through the chroma filter, and the result is written as a
-// YUV4MPEG2 stream again.
+// srcnnyuv -- YUV4MPEG2 (.y4m) video through srcnn_yuv420_upscale_dev (include/srcnn_amd_yuv.h) or, with --all-formats,
+// srcnn_yuv_upscale_dev (include/srcnn_amd_yuv_ex.h): every frame's Y plane goes through SRCNN with the chosen filter, its
+// chroma planes through the chroma filter, and the result is written as a YUV4MPEG2 stream again.
 //
-//   srcnnyuv [--scale M] [--filter nearest|bilinear|bicubic|lanczos3|bspline] IN.y4m|- OUT.y4m|-
+//   srcnnyuv [--all-formats] [--scale M] [--filter nearest|bilinear|bicubic|lanczos3|bspline] IN.y4m|- OUT.y4m|-
 //
 // Input: 8-bit 4:2:0 (C420, C420jpeg, C420paldv, C420mpeg2, or no C tag), progressive (Ip or no I tag).  Every other colour
 // space, every bit depth above 8 and interlaced input are refused with exit status 2 and a one-line message, before the
-// device is touched.  The output header is the input's with W and H replaced; every other tag and every frame's parameters
+// device is touched.  --all-formats also takes C422 and C444 and the p10 / p12 / p14 / p16 forms of C420, C422 and C444
+// (YUV4MPEG2 stores those planar, little-endian, value in the low bits); mono, alpha, any other depth and interlaced streams
+// are still refused with status 2.  The output header is the input's with W and H replaced; every other tag and every frame's parameters
 // are copied verbatim.  Frames move through two page-locked staging slots on two streams, so that the upload of frame i+1
 // overlaps the kernels of frame i.
 #include <cstdio>
@@ -17,6 +19,7 @@
 
 #include "../include/srcnn_amd.h"
 #include "../include/srcnn_amd_yuv.h"
+#include "../include/srcnn_amd_yuv_ex.h"
 
 namespace {
 
@@ -30,7 +33,7 @@ namespace {
 
 void usage()
 {
-    std::fprintf(stderr, "usage: srcnnyuv [--scale M] [--filter nearest|bilinear|bicubic|lanczos3|bspline] IN.y4m|- OUT.y4m|-\n");
+    std::fprintf(stderr, "usage: srcnnyuv [--all-formats] [--scale M] [--filter nearest|bilinear|bicubic|lanczos3|bspline] IN.y4m|- OUT.y4m|-\n");
     std::exit(2);
 }
 
@@ -71,6 +74,29 @@ struct Slot {
     bool pending = false;
 };
 
+// "C420p10" -> (SRCNN_YUV_420, 10); false for what --all-formats does not take (mono, alpha, 411, other depths)
+bool parse_colour_space(const std::string& tag, int& chroma, int& depth)
+{
+    std::string t = tag.substr(1);
+    depth = 8;
+    const size_t p = t.find('p', 3);
+    if (t.compare(0, 3, "420") == 0 && (t == "420" || t == "420jpeg" || t == "420paldv" || t == "420mpeg2")) { chroma = SRCNN_YUV_420; return true; }
+    if (t == "422") { chroma = SRCNN_YUV_422; return true; }
+    if (t == "444") { chroma = SRCNN_YUV_444; return true; }
+    if (p != 3) return false;
+    const std::string base = t.substr(0, 3), d = t.substr(4);
+    if (base == "420") chroma = SRCNN_YUV_420;
+    else if (base == "422") chroma = SRCNN_YUV_422;
+    else if (base == "444") chroma = SRCNN_YUV_444;
+    else return false;
+    if (d == "10") depth = 10;
+    else if (d == "12") depth = 12;
+    else if (d == "14") depth = 14;
+    else if (d == "16") depth = 16;
+    else return false;
+    return true;
+}
+
 void check(int rc, const char* what)
 {
     if (rc != SRCNN_OK) {
@@ -85,6 +111,7 @@ int main(int argc, char** argv)
 {
     float scale = 2.0f;
     int filter = SRCNN_FILTER_BICUBIC;
+    bool all_formats = false;
     std::vector<const char*> files;
     static const char* const kFilters[] = {"nearest", "bilinear", "bicubic", "lanczos3", "bspline"};
     for (int i = 1; i < argc; ++i) {
@@ -99,6 +126,8 @@ int main(int argc, char** argv)
             for (int k = 0; k < 5; ++k)
                 if (v == kFilters[k]) filter = k;
             if (filter < 0) die(2, "unknown filter %s", v.c_str());
+        } else if (a == "--all-formats") {
+            all_formats = true;
         } else if (a == "-h" || a == "--help") {
             usage();
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
@@ -117,19 +146,32 @@ int main(int argc, char** argv)
     std::vector<std::string> tags = split(line);
     if (tags.empty() || tags[0] != "YUV4MPEG2") die(2, "not a YUV4MPEG2 stream");
     unsigned w = 0, h = 0;
+    srcnn_yuv_format fmt = {(unsigned)sizeof(srcnn_yuv_format), SRCNN_YUV_PLANAR, SRCNN_YUV_420, 8, 0};
     for (size_t k = 1; k < tags.size(); ++k) {
         const std::string& t = tags[k];
         if (t[0] == 'W') w = (unsigned)std::strtoul(t.c_str() + 1, nullptr, 10);
         else if (t[0] == 'H') h = (unsigned)std::strtoul(t.c_str() + 1, nullptr, 10);
-        else if (t[0] == 'C' && t != "C420" && t != "C420jpeg" && t != "C420paldv" && t != "C420mpeg2")
+        else if (t[0] == 'C' && all_formats) {
+            if (!parse_colour_space(t, fmt.chroma, fmt.depth))
+                die(2, "unsupported colour space %s (4:2:0 / 4:2:2 / 4:4:4 at 8, 10, 12, 14 or 16 bits only)", t.c_str());
+        } else if (t[0] == 'C' && t != "C420" && t != "C420jpeg" && t != "C420paldv" && t != "C420mpeg2")
             die(2, "unsupported colour space %s (8-bit 4:2:0 only)", t.c_str());
         else if (t[0] == 'I' && t != "Ip") die(2, "unsupported interlacing %s (progressive only)", t.c_str());
     }
     if (w == 0 || h == 0) die(2, "missing or zero W / H");
     unsigned dw = 0, dh = 0;
     if (srcnn_output_size(w, h, scale, 0, &dw, &dh) != SRCNN_OK) die(2, "--scale gives an empty frame");
-    const size_t cw = (w + 1) / 2, ch = (h + 1) / 2, dcw = (dw + 1) / 2, dch = (dh + 1) / 2;
-    const size_t in_bytes = (size_t)w * h + 2 * cw * ch, out_bytes = (size_t)dw * dh + 2 * dcw * dch;
+    // tight planes, one after the other: [0] = Y bytes, [1] = bytes of one chroma plane
+    size_t in_plane[2], out_plane[2];
+    for (int k = 0; k < 2; ++k) {
+        unsigned rows = 0;
+        size_t rb = 0;
+        if (srcnn_yuv_plane_size(&fmt, w, h, k, nullptr, &rows, &rb) != SRCNN_OK) die(2, "%s", srcnn_last_error());
+        in_plane[k] = rb * rows;
+        if (srcnn_yuv_plane_size(&fmt, dw, dh, k, nullptr, &rows, &rb) != SRCNN_OK) die(2, "%s", srcnn_last_error());
+        out_plane[k] = rb * rows;
+    }
+    const size_t in_bytes = in_plane[0] + 2 * in_plane[1], out_bytes = out_plane[0] + 2 * out_plane[1];
 
     FILE* out = std::strcmp(files[1], "-") == 0 ? stdout : std::fopen(files[1], "wb");
     if (!out) die(2, "cannot create %s", files[1]);
@@ -170,9 +212,15 @@ int main(int argc, char** argv)
         s.params = line.substr(5);
         if (std::fread(s.pin_in, 1, in_bytes, in) != in_bytes) die(2, "truncated frame");
         check(srcnn_memcpy_h2d(s.d_in, s.pin_in, in_bytes, s.stream), "upload");
-        const unsigned char* const src[3] = {s.d_in, s.d_in + (size_t)w * h, s.d_in + (size_t)w * h + cw * ch};
-        unsigned char* const dst[3] = {s.d_out, s.d_out + (size_t)dw * dh, s.d_out + (size_t)dw * dh + dcw * dch};
-        check(srcnn_yuv420_upscale_dev(SRCNN_YUV_I420, w, h, scale, filter, src, src_pitch, dst, dst_pitch, s.stream), "srcnn_yuv420_upscale_dev");
+        const unsigned char* const src[3] = {s.d_in, s.d_in + in_plane[0], s.d_in + in_plane[0] + in_plane[1]};
+        unsigned char* const dst[3] = {s.d_out, s.d_out + out_plane[0], s.d_out + out_plane[0] + out_plane[1]};
+        if (all_formats) {
+            const void* const vsrc[3] = {src[0], src[1], src[2]};
+            void* const vdst[3] = {dst[0], dst[1], dst[2]};
+            check(srcnn_yuv_upscale_dev(&fmt, w, h, scale, filter, vsrc, src_pitch, vdst, dst_pitch, s.stream), "srcnn_yuv_upscale_dev");
+        } else {
+            check(srcnn_yuv420_upscale_dev(SRCNN_YUV_I420, w, h, scale, filter, src, src_pitch, dst, dst_pitch, s.stream), "srcnn_yuv420_upscale_dev");
+        }
         check(srcnn_memcpy_d2h(s.pin_out, s.d_out, out_bytes, s.stream), "download");
         s.pending = true;
     }
