@@ -51,13 +51,20 @@ DEBUG_SYMBOLS = [
 YUV_SYMBOLS = ["srcnn_yuv_abi_version", "srcnn_yuv420_upscale_dev"]
 # the high-bit-depth / 4:2:2 / 4:4:4 YUV extension (include/srcnn_amd_yuv_ex.h, listed in include/srcnn_amd_yuv_ex.abi; its own version)
 YUV_EX_SYMBOLS = ["srcnn_yuv_ex_abi_version", "srcnn_yuv_plane_size", "srcnn_yuv_upscale_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS   # everything the library exports besides the two C++ symbols
+# RGB(A) images already in device memory (include/srcnn_amd_rgb.h, listed in include/srcnn_amd_rgb.abi; its own version)
+RGB_SYMBOLS = ["srcnn_rgb_abi_version", "srcnn_rgb_plane_size", "srcnn_rgb_upscale_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
 class YuvFormat(C.Structure):
     """srcnn_yuv_format (include/srcnn_amd_yuv_ex.h)."""
     _fields_ = [("struct_size", C.c_uint), ("layout", C.c_int), ("chroma", C.c_int), ("depth", C.c_int), ("msb_aligned", C.c_int)]
+
+
+class RgbFormat(C.Structure):
+    """srcnn_rgb_format (include/srcnn_amd_rgb.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("layout", C.c_int), ("order", C.c_int), ("alpha", C.c_int), ("depth", C.c_int)]
 
 
 class SrcnnError(RuntimeError):
@@ -136,9 +143,12 @@ def lib():
             "srcnn_yuv_ex_abi_version": (i, []),
             "srcnn_yuv_plane_size": (i, [C.POINTER(YuvFormat), u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(sz)]),
             "srcnn_yuv_upscale_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp]),
+            "srcnn_rgb_abi_version": (i, []),
+            "srcnn_rgb_plane_size": (i, [C.POINTER(RgbFormat), u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(sz)]),
+            "srcnn_rgb_upscale_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -592,6 +602,159 @@ def yuv_upscale(planes, layout="planar", chroma="420", depth=8, msb_aligned=Fals
     else:
         check(lib().srcnn_stream_sync(stream))
     return tuple(b.to_numpy(dt, s) for b, s in zip(dout, shapes))
+
+
+RGB_INTERLEAVED, RGB_PLANAR = 0, 1
+RGB_ORDER_RGB, RGB_ORDER_BGR = 0, 1
+_RGB_LAYOUTS = {"interleaved": RGB_INTERLEAVED, "hwc": RGB_INTERLEAVED, "planar": RGB_PLANAR, "chw": RGB_PLANAR}
+_RGB_ORDERS = {"rgb": RGB_ORDER_RGB, "rgba": RGB_ORDER_RGB, "bgr": RGB_ORDER_BGR, "bgra": RGB_ORDER_BGR}
+
+
+def rgb_format(layout="interleaved", order="rgb", alpha=False, depth=8):
+    """A srcnn_rgb_format: layout "interleaved" | "planar", order "rgb" | "bgr" (or the SRCNN_RGB_* values), alpha for a
+    fourth channel, depth 8 / 10 / 12 / 14 / 16.  Unknown values are passed on for the library to refuse."""
+    layout = layout.lower() if isinstance(layout, str) else layout
+    order = order.lower() if isinstance(order, str) else order
+    return RgbFormat(C.sizeof(RgbFormat), int(_RGB_LAYOUTS.get(layout, layout)), int(_RGB_ORDERS.get(order, order)), int(alpha), int(depth))
+
+
+def rgb_plane_size(fmt, w, h, plane):
+    """(cols, rows, row_bytes) of one plane of a w x h image (srcnn_rgb_plane_size; no device)."""
+    c, r, b = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
+    check(lib().srcnn_rgb_plane_size(C.byref(fmt), int(w), int(h), int(plane), C.byref(c), C.byref(r), C.byref(b)))
+    return c.value, r.value, b.value
+
+
+def rgb_upscale_dev(fmt, w, h, multiply, filt, src, src_pitch, dst, dst_pitch, dst_conv=None, dst_conv_pitch=0, stream=None):
+    """srcnn_rgb_upscale_dev on device memory, as given: fmt an RgbFormat (rgb_format(...)) or None, src / dst up to 4 plane
+    arguments (see _addr; interleaved uses the first only), pitches byte counts (0 = tight) or None, dst_conv a plane
+    argument for the truncated Y' or None.  Asynchronous on `stream` (a Stream, a raw handle or None); raises SrcnnError with
+    the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    four = lambda xs, fill: list(xs) + [fill] * (4 - len(xs))   # noqa: E731
+    s = (vp * 4)(*[_addr(p) for p in four(src, None)]) if src is not None else None
+    d = (vp * 4)(*[_addr(p) for p in four(dst, None)]) if dst is not None else None
+    sp = (sz * 4)(*four(src_pitch, 0)) if src_pitch is not None else None
+    dp = (sz * 4)(*four(dst_pitch, 0)) if dst_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_rgb_upscale_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)),
+                                      int(filt), s, sp, d, dp, _addr(dst_conv), int(dst_conv_pitch), handle))
+
+
+def rgb_upscale(image, multiply=2.0, filt=SRCNNF_Bicubic, layout=None, order="rgb", depth=None, want_conv=False, stream=None):
+    """One RGB(A) image through srcnn_rgb_upscale_dev: numpy in, numpy out, uint8 at depth 8 and uint16 above.  image is
+    (h, w, c) (interleaved) or (c, h, w) (planar) with c = 3 or 4; layout = "interleaved" / "planar" decides where both fit
+    (default: interleaved when the last axis is 3 or 4).  depth defaults to 8 for uint8 and 16 otherwise.
+    Returns (out, conv | None) with out shaped like the input."""
+    image = np.asarray(image)
+    if image.ndim != 3:
+        raise ValueError("an RGB(A) image is (h, w, c) or (c, h, w), not %r" % (image.shape,))
+    if layout is None:
+        layout = "interleaved" if image.shape[2] in (3, 4) else "planar"
+    planar = _RGB_LAYOUTS.get(layout.lower() if isinstance(layout, str) else layout, layout) == RGB_PLANAR
+    if depth is None:
+        depth = 8 if image.dtype == np.uint8 else 16
+    dt = np.uint8 if depth == 8 else np.uint16
+    image = np.ascontiguousarray(image, dt)
+    (c, h, w) = image.shape if planar else (image.shape[2], image.shape[0], image.shape[1])
+    if c not in (3, 4):
+        raise ValueError("%d channels: an RGB(A) image has 3 or 4" % c)
+    fmt = rgb_format(RGB_PLANAR if planar else RGB_INTERLEAVED, order, c == 4, depth)
+    dw, dh = output_size(w, h, multiply)
+    bps = np.dtype(dt).itemsize
+    din = DeviceBuffer.from_numpy(image)
+    dout = DeviceBuffer(max(1, dw * dh * c * bps))
+    dconv = DeviceBuffer(max(1, dw * dh * bps)) if want_conv else None
+    if planar:
+        src = [(din, k * w * h * bps) for k in range(c)]
+        dst = [(dout, k * dw * dh * bps) for k in range(c)]
+    else:
+        src, dst = [din], [dout]
+    rgb_upscale_dev(fmt, w, h, multiply, filt, src, None, dst, None, dconv, 0, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    out = dout.to_numpy(dt, (c, dh, dw) if planar else (dh, dw, c))
+    return out, (dconv.to_numpy(dt, (dh, dw)) if want_conv else None)
+
+
+def _one_hip_runtime():
+    """torch wheels carry a HIP runtime of their own.  When torch is imported first this library binds to that copy and both
+    share one runtime; the other way round the process holds two, and memory of one is unknown to the other."""
+    seen = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                path = line.rsplit(None, 1)[-1]
+                if "/libamdhip64.so" in path:
+                    seen.add(os.path.realpath(path))
+    except OSError:
+        return
+    if len(seen) > 1:
+        raise RuntimeError("two HIP runtimes are loaded (%s): import torch before the first libsrcnn_amd call so that both use "
+                           "the same one" % ", ".join(sorted(seen)))
+
+
+def rgb_upscale_torch(t, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=False, order="rgb", depth=None):
+    """srcnn_rgb_upscale_dev on a torch tensor that lives on a GPU: t is torch.uint8 (depth 8) or a 16-bit integer tensor
+    (depth 16 unless `depth` says 10 / 12 / 14), shaped (H, W, C) or (C, H, W) with C in (3, 4).  The memory behind it must be
+    interleaved pixels (channel stride 1, column stride C) or one plane per channel (column stride 1); rows may be padded --
+    the pitch is taken from the strides -- and anything else raises ValueError.  The output tensor (and the truncated Y'
+    plane with want_conv) is allocated by torch on the same device, in the same layout; the call is queued on
+    torch.cuda.current_stream() and neither copies to the host nor synchronises.  Returns (out, conv | None).
+    The tensor's device must be the device of the calling thread's current srcnn context."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("rgb_upscale_torch needs a torch tensor on a GPU")
+    sixteen = [torch.int16] + ([torch.uint16] if hasattr(torch, "uint16") else [])
+    if t.dtype != torch.uint8 and t.dtype not in sixteen:
+        raise ValueError("dtype %s: torch.uint8 or a 16-bit integer type" % (t.dtype,))
+    bps = 1 if t.dtype == torch.uint8 else 2
+    if depth is None:
+        depth = 8 if bps == 1 else 16
+    if (depth == 8) != (bps == 1):
+        raise ValueError("depth %d does not go with %s" % (depth, t.dtype))
+    if t.dim() != 3 or 0 in t.shape:
+        raise ValueError("an RGB(A) image is (H, W, C) or (C, H, W), not %r" % (tuple(t.shape),))
+    lay = None
+    for hwc in (True, False):            # which axis carries the channels, and what the strides say about the memory
+        (H, W, Cn) = tuple(t.shape) if hwc else (t.shape[1], t.shape[2], t.shape[0])
+        (sh, sw, sc) = t.stride() if hwc else (t.stride(1), t.stride(2), t.stride(0))
+        if Cn not in (3, 4):
+            continue
+        if sc == 1 and sw == Cn and sh >= W * Cn:
+            lay = (hwc, RGB_INTERLEAVED, H, W, Cn, sh, sc)
+        elif sw == 1 and sh >= W and sc >= 1:
+            lay = (hwc, RGB_PLANAR, H, W, Cn, sh, sc)
+        if lay:
+            break
+    if lay is None:
+        raise ValueError("shape %r with strides %r is neither interleaved pixels nor one plane per channel" % (tuple(t.shape), t.stride()))
+    hwc, layout, H, W, Cn, sh, sc = lay
+    lib()
+    _one_hip_runtime()
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    if lib().srcnn_context_count() == 0:
+        init(dev)
+    have = lib().srcnn_context_device(lib().srcnn_get_context())
+    if have != dev:
+        raise ValueError("the tensor lives on device %d, the current srcnn context on device %d (set_context)" % (dev, have))
+    dw, dh = output_size(W, H, multiply)
+    if layout == RGB_INTERLEAVED:
+        out = torch.empty((dh, dw, Cn), dtype=t.dtype, device=t.device)
+        src, dst = [t.data_ptr()], [out.data_ptr()]
+        result = out if hwc else out.permute(2, 0, 1)
+    else:
+        out = torch.empty((Cn, dh, dw), dtype=t.dtype, device=t.device)
+        src = [t.data_ptr() + k * sc * bps for k in range(Cn)]
+        dst = [out.data_ptr() + k * dh * dw * bps for k in range(Cn)]
+        result = out.permute(1, 2, 0) if hwc else out
+    conv = torch.empty((dh, dw), dtype=t.dtype, device=t.device) if want_conv else None
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    rgb_upscale_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), dst, None,
+                    conv.data_ptr() if want_conv else None, 0, stream or None)
+    return result, conv
 
 
 class PinnedArray:

@@ -27,8 +27,10 @@
 
 #include "srcnn_host.hpp"
 #include "srcnn_yuv.h"
+#include "srcnn_rgb.h"
 #include "../../include/srcnn_amd_yuv.h"
 #include "../../include/srcnn_amd_yuv_ex.h"
+#include "../../include/srcnn_amd_rgb.h"
 
 namespace srcnn {
 
@@ -1310,6 +1312,147 @@ int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, un
     return SRCNN_OK;
 }
 
+// ---- RGB(A) images (include/srcnn_amd_rgb.h) ----
+
+// srcnn_rgb_format -> RgbRule, or SRCNN_E_ARG
+int rgb_rule_from_format(const srcnn_rgb_format* f, RgbRule& g)
+{
+    if (!f) return fail(SRCNN_E_ARG, "NULL format");
+    if (f->struct_size != sizeof(srcnn_rgb_format)) return fail(SRCNN_E_ARG, "struct_size %u is not %zu", f->struct_size, sizeof(srcnn_rgb_format));
+    if (f->layout != SRCNN_RGB_INTERLEAVED && f->layout != SRCNN_RGB_PLANAR) return fail(SRCNN_E_ARG, "unknown RGB layout %d", f->layout);
+    if (f->order != SRCNN_RGB_ORDER_RGB && f->order != SRCNN_RGB_ORDER_BGR) return fail(SRCNN_E_ARG, "unknown channel order %d", f->order);
+    if (f->alpha != 0 && f->alpha != 1) return fail(SRCNN_E_ARG, "bad alpha %d", f->alpha);
+    if (f->depth != 8 && f->depth != 10 && f->depth != 12 && f->depth != 14 && f->depth != 16) return fail(SRCNN_E_ARG, "unsupported depth %d", f->depth);
+    g.planar = f->layout == SRCNN_RGB_PLANAR;
+    g.bgr = f->order == SRCNN_RGB_ORDER_BGR;
+    g.ch = 3 + f->alpha;
+    g.bps = f->depth == 8 ? 1 : 2;
+    g.mask = (1u << f->depth) - 1u;
+    g.up = (float)(1u << (f->depth - 8));
+    g.down = 1.f / g.up;
+    return SRCNN_OK;
+}
+
+// Everything srcnn_rgb_upscale_dev refuses beyond the format itself, checked before any device lookup.  conv.lo stays NULL
+// when the caller asks for no truncated Y' plane.
+int check_rgb_args(const RgbRule& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[4],
+                   const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4], void* dst_conv,
+                   size_t dst_conv_pitch, unsigned& dw, unsigned& dh, YuvPlane in[4], YuvPlane out[4], YuvPlane& conv)
+{
+    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    const int np = g.planar ? g.ch : 1;
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
+    for (int k = 0; k < np; ++k)
+        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
+    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
+    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
+    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
+        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
+    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
+    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
+        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
+    auto describe = [&](YuvPlane& p, const void* base, size_t pitch, size_t row_bytes, unsigned rows, const char* what, int k) -> int {
+        p.lo = static_cast<const unsigned char*>(base);
+        p.row_bytes = row_bytes;
+        p.rows = rows;
+        p.pitch = pitch ? pitch : row_bytes;
+        if (p.pitch < p.row_bytes) return fail(SRCNN_E_ARG, "%s pitch %zu of plane %d is below its row of %zu bytes", what, p.pitch, k, p.row_bytes);
+        if (g.bps == 2 && ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & 1))
+            return fail(SRCNN_E_ARG, "%s plane %d: 16-bit samples need an even base address and pitch", what, k);
+        return SRCNN_OK;
+    };
+    const size_t spp = g.planar ? 1 : (size_t)g.ch;                 // samples per pixel of one plane
+    int rc;
+    for (int k = 0; k < np; ++k) {
+        if ((rc = describe(in[k], src[k], src_pitch ? src_pitch[k] : 0, (size_t)g.bps * spp * w, h, "input", k))) return rc;
+        if ((rc = describe(out[k], dst[k], dst_pitch ? dst_pitch[k] : 0, (size_t)g.bps * spp * dw, dh, "output", k))) return rc;
+    }
+    int nout = np;
+    if (dst_conv) {
+        if ((rc = describe(conv, dst_conv, dst_conv_pitch, (size_t)g.bps * dw, dh, "dst_conv", 0))) return rc;
+        out[nout++] = conv;                                         // (np <= 4: the caller's array has room for five)
+    }
+    for (int a = 0; a < np; ++a)
+        for (int b = 0; b < nout; ++b)
+            if (overlaps(in[a], out[b])) return fail(SRCNN_E_ARG, "input plane %d overlaps output plane %d", a, b);
+    for (int a = 0; a < nout; ++a)
+        for (int b = a + 1; b < nout; ++b)
+            if (overlaps(out[a], out[b])) return fail(SRCNN_E_ARG, "output planes %d and %d overlap", a, b);
+    return SRCNN_OK;
+}
+
+// The reference's own format (8-bit interleaved R,G,B[,A], tight rows, an up-scale in both axes) goes through the fused shell
+// of srcnn_process_u8: Y' from the interleaved source (k_rs2d), then the merge with on-the-fly chroma -- no float plane of
+// source or destination size.  Everything else: unpack -> per band { Y path, chroma / alpha resample, pack }.  conv.lo == NULL:
+// no truncated Y' plane.
+int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
+              const YuvPlane out[4], const YuvPlane& conv)
+{
+    Workspace& ws = *c.ws;
+    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    int rc;
+    const bool tight = in[0].pitch == in[0].row_bytes && out[0].pitch == out[0].row_bytes && (!conv.lo || conv.pitch == conv.row_bytes);
+    // (as in process_share: the switches that force the plane resamplers select the plane shell as well)
+    bool fused_shell = g.bps == 1 && !g.planar && !g.bgr && tight && !settings().shell_unfused && !settings().resample_2pass && dw > w && dh > h;
+    TableRef cv, ch_, yv, yh;
+    if (fused_shell) {
+        if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
+        if ((rc = get_table(c, cfilter, dw, w, ch_))) return rc;
+        if ((rc = get_table(c, filter, dh, h, yv))) return rc;
+        if ((rc = get_table(c, filter, dw, w, yh))) return rc;
+        fused_shell = rs2d_fits(1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, yv->view(), yh->view()) &&
+                      rs2d_fits(g.ch - 1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, cv->view(), ch_->view());
+    }
+    if (fused_shell) {
+        if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)dw * band))) return rc;
+        float* yp = ws.planes;
+        const YSource ysrc = YSource::from_rgb(in[0].lo, g.ch);
+        unsigned char* d_out = const_cast<unsigned char*>(out[0].lo);
+        unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
+        for (unsigned a = 0; a < dh; a += band) {
+            const unsigned b = std::min(dh, a + band);
+            if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, yp))) return rc;
+            const size_t p0 = (size_t)a * dw;
+            if (!launch_merge_fused(in[0].lo, (int)w, (int)h, g.ch, yp, d_out + p0 * g.ch, d_conv ? d_conv + p0 : nullptr, (int)dw,
+                                    (int)dh, (int)a, (int)(b - a), cv->view(), ch_->view(), c.s))
+                return fail(SRCNN_E_UNSUPPORTED, "fused colour shell refused a shape it was selected for");
+        }
+        HIP_TRY(hipGetLastError());
+        return SRCNN_OK;
+    }
+    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels):
+    // [Y Cb Cr (A) at source size] [Y' Cb' Cr' (A') of one band]
+    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t sn = up64((size_t)w * h), bn = up64((size_t)dw * band);
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)g.ch * (sn + bn)))) return rc;
+    float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* dp[4] = {nullptr, nullptr, nullptr, nullptr};
+    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
+    for (int k = 0; k < g.ch; ++k) {
+        sp[k] = ws.planes + (size_t)k * sn;
+        dp[k] = ws.planes + (size_t)g.ch * sn + (size_t)k * bn;
+    }
+    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
+        src[k] = in[k].lo; spitch[k] = in[k].pitch;
+        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
+    }
+    launch_rgb_unpack(g, src, spitch, w, h, sp, c.s);
+    const YSource ysrc = YSource::from_plane(sp[0]);
+    for (unsigned a = 0; a < dh; a += band) {
+        const unsigned b = std::min(dh, a + band);
+        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, dp[0]))) return rc;
+        for (int k = 1; k < g.ch; ++k)
+            if ((rc = resample_rows_range(c, sp[k], w, h, dw, dh, cfilter, a, b, dp[k]))) return rc;
+        launch_rgb_pack(g, dp, dw, b - a, dst, dpitch, a, const_cast<unsigned char*>(conv.lo), conv.pitch, c.s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 }  // namespace
 }  // namespace srcnn
 
@@ -1946,6 +2089,40 @@ int srcnn_yuv_upscale_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, f
     if (sc.rc) return sc.rc;
     TraceRange tr("srcnn yuv %ux%u -> %ux%u", w, h, dw, dh);
     return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- RGB(A) images in device memory (include/srcnn_amd_rgb.h) ----
+int srcnn_rgb_abi_version(void) { return SRCNN_AMD_RGB_VERSION; }
+
+int srcnn_rgb_plane_size(const srcnn_rgb_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
+                         size_t* row_bytes)
+{
+    RgbRule g;
+    int rc;
+    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    if (plane < 0 || plane > 3) return fail(SRCNN_E_ARG, "plane %d", plane);
+    const bool used = g.planar ? plane < g.ch : plane == 0;
+    if (cols) *cols = used ? w : 0;
+    if (rows) *rows = used ? h : 0;
+    if (row_bytes) *row_bytes = used ? (size_t)g.bps * w * (g.planar ? 1 : g.ch) : 0;
+    return SRCNN_OK;
+}
+
+int srcnn_rgb_upscale_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                          const void* const src[4], const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4],
+                          void* dst_conv, size_t dst_conv_pitch, void* stream)
+{
+    RgbRule g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[4], out[5], conv;
+    int rc;
+    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
+    if ((rc = check_rgb_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, dw, dh, in, out, conv))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn rgb %ux%u -> %ux%u", w, h, dw, dh);
+    return rgb_frame(sc.c, g, w, h, dw, dh, filter, in, out, conv);
 }
 
 }  // extern "C"

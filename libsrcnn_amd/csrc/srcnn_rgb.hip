@@ -1,0 +1,319 @@
+// srcnn_rgb.hip -- the conversions around the SRCNN path for RGB(A) images that live in device memory
+// (include/srcnn_amd_rgb.h): interleaved or planar samples, 8-bit or 16-bit words, either channel order, pitched rows.
+//
+//   k_rgb_unpack   integer plane(s) -> tight float32 planes Y, Cb, Cr (and A)
+//                  value = word & maxv;  R, G, B, A = (float)value * 2^-s (exact);  then the split of k_rgb_split
+//                  (src/libsrcnn.cpp:233-272): every product and every sum rounded on its own, no contraction
+//   k_rgb_pack     tight float32 rows Y', Cb', Cr' (and A') -> destination rows of the integer plane(s), and optionally the
+//                  truncated Y' plane; the merge of k_ycc_merge (src/libsrcnn.cpp:274-308), then
+//                  sample = (unsigned)(MAX(0, MIN(255, v)) * 2^s) in the reference's macro forms
+//
+// Both kernels are memory-bound and move 4 pixels per thread: the float side as one 16-byte access per plane, the integer
+// side as the 1 .. 8 consecutive dwords that hold the 4 pixels (12 / 16 / 24 / 32 bytes interleaved, 4 / 8 bytes per plane
+// planar; consecutive dwords are merged into wider accesses by the compiler), where bases and pitches are aligned for it
+// (decided once per launch); a row's last partial chunk and misaligned planes take the scalar forms, so that no byte outside a
+// row's samples is ever touched.  Grid-stride over rows x chunks.  mask and the two scalings are kernel arguments: every depth
+// runs the same instances.  The host side is srcnn_capi.cpp (srcnn_rgb_upscale_dev).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "srcnn_rgb.h"
+
+#pragma clang fp contract(off)
+
+namespace srcnn {
+
+namespace {
+
+constexpr unsigned kChunkRgb = 4;        // pixels per thread
+
+struct RgbIo {
+    unsigned char* p[4];                 // integer planes (interleaved: p[0] only)
+    size_t pitch[4];
+    float* f[4];                         // float planes Y, Cb, Cr, A: tight, w floats per row
+    unsigned char* conv;                 // pack only: truncated Y', or NULL
+    size_t conv_pitch;
+    unsigned w, rows, row0;              // row0: pack only, the destination row of float row 0
+    unsigned mask;
+    float down, up;
+    int bgr;
+    int int_vec, flt_vec, conv_vec;      // dword accesses of the integer planes / float4 accesses / dword stores of conv are aligned
+};
+
+// sample j of the 4 * D (interleaved) or 4 (planar) samples packed in consecutive dwords
+template <int BPS>
+__device__ __forceinline__ unsigned sample_of(const unsigned* wd, int j)
+{
+    if constexpr (BPS == 1) return (wd[j >> 2] >> (8 * (j & 3))) & 0xffu;
+    else return (wd[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+}
+
+template <int BPS>
+__device__ __forceinline__ void put_sample(unsigned* wd, int j, unsigned v)
+{
+    if constexpr (BPS == 1) wd[j >> 2] |= v << (8 * (j & 3));
+    else wd[j >> 1] |= v << (16 * (j & 1));
+}
+
+template <int BPS>
+__device__ __forceinline__ unsigned load_scalar(const unsigned char* q)
+{
+    if constexpr (BPS == 1) return *q;
+    else return *reinterpret_cast<const unsigned short*>(q);     // 2-byte aligned: the host refuses odd planes
+}
+
+template <int BPS>
+__device__ __forceinline__ void store_scalar(unsigned char* q, unsigned v)
+{
+    if constexpr (BPS == 1) *q = (unsigned char)v;
+    else *reinterpret_cast<unsigned short*>(q) = (unsigned short)v;
+}
+
+__device__ __forceinline__ unsigned to_code(float v, float up)
+{   // MIN(255.f, v) then MAX(0.f, .) in the reference's macro forms, the exact scaling, the truncating cast
+    v = (255.f < v) ? 255.f : v;
+    v = (0.f > v) ? 0.f : v;
+    return (unsigned)(v * up);
+}
+
+template <int BPS, bool PLANAR, int D>
+__global__ __launch_bounds__(256) void k_rgb_unpack(const RgbIo a)
+{
+    const unsigned cpr = (a.w + kChunkRgb - 1) / kChunkRgb;
+    const unsigned total = cpr * a.rows;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned r = i / cpr, c = (i - r * cpr) * kChunkRgb;
+        const unsigned n = min(kChunkRgb, a.w - c);
+        unsigned v[kChunkRgb][D];        // [pixel][channel in memory order]
+        if (n == kChunkRgb && a.int_vec) {
+            if constexpr (PLANAR) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    const unsigned* q = reinterpret_cast<const unsigned*>(a.p[k] + (size_t)r * a.pitch[k] + (size_t)c * BPS);
+                    unsigned wd[BPS];
+#pragma unroll
+                    for (int t = 0; t < BPS; ++t) wd[t] = q[t];
+#pragma unroll
+                    for (int px = 0; px < (int)kChunkRgb; ++px) v[px][k] = sample_of<BPS>(wd, px);
+                }
+            } else {
+                const unsigned* q = reinterpret_cast<const unsigned*>(a.p[0] + (size_t)r * a.pitch[0] + (size_t)c * D * BPS);
+                unsigned wd[D * BPS];
+#pragma unroll
+                for (int t = 0; t < D * BPS; ++t) wd[t] = q[t];
+#pragma unroll
+                for (int px = 0; px < (int)kChunkRgb; ++px)
+#pragma unroll
+                    for (int k = 0; k < D; ++k) v[px][k] = sample_of<BPS>(wd, px * D + k);
+            }
+        } else {
+#pragma unroll
+            for (int px = 0; px < (int)kChunkRgb; ++px)
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    v[px][k] = 0;
+                    if ((unsigned)px < n) {
+                        const unsigned char* q = PLANAR ? a.p[k] + (size_t)r * a.pitch[k] + (size_t)(c + px) * BPS
+                                                        : a.p[0] + (size_t)r * a.pitch[0] + ((size_t)(c + px) * D + k) * BPS;
+                        v[px][k] = load_scalar<BPS>(q);
+                    }
+                }
+        }
+        float yv[kChunkRgb], cbv[kChunkRgb], crv[kChunkRgb], av[kChunkRgb];
+#pragma unroll
+        for (int px = 0; px < (int)kChunkRgb; ++px) {
+            float ch[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < D; ++k) ch[k] = (float)(v[px][k] & a.mask) * a.down;
+            const float r_ = a.bgr ? ch[2] : ch[0], g = ch[1], b = a.bgr ? ch[0] : ch[2];
+            yv[px] = (0.299f * r_) + (0.587f * g) + (0.114f * b);                 // src/libsrcnn.cpp:251-256
+            cbv[px] = 128.f - (0.1687f * r_) - (0.3313f * g) + (0.5f * b);
+            crv[px] = 128.f + (0.5f * r_) - (0.4187f * g) - (0.0813f * b);
+            av[px] = ch[3];
+        }
+        const size_t o = (size_t)r * a.w + c;
+        if (n == kChunkRgb && a.flt_vec) {
+            *reinterpret_cast<float4*>(a.f[0] + o) = make_float4(yv[0], yv[1], yv[2], yv[3]);
+            *reinterpret_cast<float4*>(a.f[1] + o) = make_float4(cbv[0], cbv[1], cbv[2], cbv[3]);
+            *reinterpret_cast<float4*>(a.f[2] + o) = make_float4(crv[0], crv[1], crv[2], crv[3]);
+            if constexpr (D == 4) *reinterpret_cast<float4*>(a.f[3] + o) = make_float4(av[0], av[1], av[2], av[3]);
+        } else {
+#pragma unroll
+            for (int px = 0; px < (int)kChunkRgb; ++px) {
+                if ((unsigned)px < n) {
+                    a.f[0][o + px] = yv[px];
+                    a.f[1][o + px] = cbv[px];
+                    a.f[2][o + px] = crv[px];
+                    if constexpr (D == 4) a.f[3][o + px] = av[px];
+                }
+            }
+        }
+    }
+}
+
+template <int BPS, bool PLANAR, int D>
+__global__ __launch_bounds__(256) void k_rgb_pack(const RgbIo a)
+{
+    const unsigned cpr = (a.w + kChunkRgb - 1) / kChunkRgb;
+    const unsigned total = cpr * a.rows;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned r = i / cpr, c = (i - r * cpr) * kChunkRgb;
+        const unsigned n = min(kChunkRgb, a.w - c);
+        const size_t o = (size_t)r * a.w + c;
+        const size_t dr = (size_t)a.row0 + r;                    // destination row
+        float yv[kChunkRgb], cbv[kChunkRgb], crv[kChunkRgb], av[kChunkRgb];
+        if (n == kChunkRgb && a.flt_vec) {
+            const float4 y4 = *reinterpret_cast<const float4*>(a.f[0] + o);
+            const float4 cb4 = *reinterpret_cast<const float4*>(a.f[1] + o);
+            const float4 cr4 = *reinterpret_cast<const float4*>(a.f[2] + o);
+            float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (D == 4) a4 = *reinterpret_cast<const float4*>(a.f[3] + o);
+            yv[0] = y4.x; yv[1] = y4.y; yv[2] = y4.z; yv[3] = y4.w;
+            cbv[0] = cb4.x; cbv[1] = cb4.y; cbv[2] = cb4.z; cbv[3] = cb4.w;
+            crv[0] = cr4.x; crv[1] = cr4.y; crv[2] = cr4.z; crv[3] = cr4.w;
+            av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
+        } else {
+#pragma unroll
+            for (int px = 0; px < (int)kChunkRgb; ++px) {
+                const bool in = (unsigned)px < n;
+                yv[px] = in ? a.f[0][o + px] : 0.f;
+                cbv[px] = in ? a.f[1][o + px] : 0.f;
+                crv[px] = in ? a.f[2][o + px] : 0.f;
+                av[px] = 0.f;
+                if constexpr (D == 4) av[px] = in ? a.f[3][o + px] : 0.f;
+            }
+        }
+        unsigned code[kChunkRgb][D], cv[kChunkRgb];              // [pixel][channel in memory order]
+#pragma unroll
+        for (int px = 0; px < (int)kChunkRgb; ++px) {
+            const float fy = yv[px], cb = cbv[px] - 128.f, cr = crv[px] - 128.f;   // src/libsrcnn.cpp:287-307
+            const unsigned R = to_code(fy + 45.f * cr / 32.f, a.up);
+            const unsigned G = to_code(fy - (11.f * cb + 23.f * cr) / 32.f, a.up);
+            const unsigned B = to_code(fy + 113.f * cb / 64.f, a.up);
+            code[px][0] = a.bgr ? B : R;
+            code[px][1] = G;
+            code[px][2] = a.bgr ? R : B;
+            if constexpr (D == 4) code[px][3] = to_code(av[px], a.up);
+            cv[px] = (unsigned)(fy * a.up);
+        }
+        if (n == kChunkRgb && a.int_vec) {
+            if constexpr (PLANAR) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    unsigned wd[BPS] = {};
+#pragma unroll
+                    for (int px = 0; px < (int)kChunkRgb; ++px) put_sample<BPS>(wd, px, code[px][k]);
+                    unsigned* q = reinterpret_cast<unsigned*>(a.p[k] + dr * a.pitch[k] + (size_t)c * BPS);
+#pragma unroll
+                    for (int t = 0; t < BPS; ++t) q[t] = wd[t];
+                }
+            } else {
+                unsigned wd[D * BPS] = {};
+#pragma unroll
+                for (int px = 0; px < (int)kChunkRgb; ++px)
+#pragma unroll
+                    for (int k = 0; k < D; ++k) put_sample<BPS>(wd, px * D + k, code[px][k]);
+                unsigned* q = reinterpret_cast<unsigned*>(a.p[0] + dr * a.pitch[0] + (size_t)c * D * BPS);
+#pragma unroll
+                for (int t = 0; t < D * BPS; ++t) q[t] = wd[t];
+            }
+        } else {
+#pragma unroll
+            for (int px = 0; px < (int)kChunkRgb; ++px)
+#pragma unroll
+                for (int k = 0; k < D; ++k)
+                    if ((unsigned)px < n) {
+                        unsigned char* q = PLANAR ? a.p[k] + dr * a.pitch[k] + (size_t)(c + px) * BPS
+                                                  : a.p[0] + dr * a.pitch[0] + ((size_t)(c + px) * D + k) * BPS;
+                        store_scalar<BPS>(q, code[px][k]);
+                    }
+        }
+        if (a.conv) {
+            unsigned char* q = a.conv + dr * a.conv_pitch + (size_t)c * BPS;
+            if (n == kChunkRgb && a.conv_vec) {
+                unsigned wd[BPS] = {};
+#pragma unroll
+                for (int px = 0; px < (int)kChunkRgb; ++px) put_sample<BPS>(wd, px, cv[px]);
+#pragma unroll
+                for (int t = 0; t < BPS; ++t) reinterpret_cast<unsigned*>(q)[t] = wd[t];
+            } else {
+#pragma unroll
+                for (int px = 0; px < (int)kChunkRgb; ++px)
+                    if ((unsigned)px < n) store_scalar<BPS>(q + (size_t)px * BPS, cv[px]);
+            }
+        }
+    }
+}
+
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+dim3 grid_for(unsigned w, unsigned rows)
+{
+    const size_t total = (size_t)((w + kChunkRgb - 1) / kChunkRgb) * rows;
+    return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 8192)));
+}
+
+RgbIo io_of(const RgbRule& f, unsigned char* const p[4], const size_t pitch[4], float* const fl[4], unsigned w, unsigned rows)
+{
+    RgbIo a{};
+    const int np = f.planar ? f.ch : 1;
+    a.int_vec = 1;
+    for (int k = 0; k < np; ++k) {
+        a.p[k] = p[k]; a.pitch[k] = pitch[k];
+        a.int_vec = a.int_vec && aligned_to(p[k], 4) && pitch[k] % 4 == 0;
+    }
+    a.flt_vec = w % 4 == 0;
+    for (int k = 0; k < f.ch; ++k) {
+        a.f[k] = fl[k];
+        a.flt_vec = a.flt_vec && aligned_to(fl[k], 16);
+    }
+    a.w = w; a.rows = rows;
+    a.mask = f.mask; a.down = f.down; a.up = f.up; a.bgr = f.bgr ? 1 : 0;
+    return a;
+}
+
+#define RGB_DISPATCH(KERNEL, f, grid, s, a)                                                                                  \
+    do {                                                                                                                     \
+        const int sel = ((f).bps == 2 ? 4 : 0) | ((f).planar ? 2 : 0) | ((f).ch == 4 ? 1 : 0);                               \
+        switch (sel) {                                                                                                       \
+        case 0: hipLaunchKernelGGL((KERNEL<1, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
+        case 1: hipLaunchKernelGGL((KERNEL<1, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        case 2: hipLaunchKernelGGL((KERNEL<1, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
+        case 3: hipLaunchKernelGGL((KERNEL<1, true, 4>), grid, dim3(256), 0, s, a); break;                                   \
+        case 4: hipLaunchKernelGGL((KERNEL<2, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
+        case 5: hipLaunchKernelGGL((KERNEL<2, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        case 6: hipLaunchKernelGGL((KERNEL<2, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
+        default: hipLaunchKernelGGL((KERNEL<2, true, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        }                                                                                                                    \
+    } while (0)
+
+}  // namespace
+
+void launch_rgb_unpack(const RgbRule& f, const unsigned char* const src[4], const size_t pitch[4], unsigned w, unsigned rows,
+                       float* const out[4], hipStream_t s)
+{
+    if (w == 0 || rows == 0) return;
+    unsigned char* p[4];
+    for (int k = 0; k < 4; ++k) p[k] = const_cast<unsigned char*>(src[k]);      // (the unpack kernel only reads them)
+    const RgbIo a = io_of(f, p, pitch, out, w, rows);
+    const dim3 grid = grid_for(w, rows);
+    RGB_DISPATCH(k_rgb_unpack, f, grid, s, a);
+}
+
+void launch_rgb_pack(const RgbRule& f, const float* const in[4], unsigned w, unsigned rows, unsigned char* const dst[4],
+                     const size_t pitch[4], unsigned row0, unsigned char* conv, size_t conv_pitch, hipStream_t s)
+{
+    if (w == 0 || rows == 0) return;
+    float* fl[4];
+    for (int k = 0; k < 4; ++k) fl[k] = const_cast<float*>(in[k]);              // (the pack kernel only reads them)
+    RgbIo a = io_of(f, dst, pitch, fl, w, rows);
+    a.row0 = row0;
+    a.conv = conv; a.conv_pitch = conv_pitch;
+    a.conv_vec = conv && aligned_to(conv, 4) && conv_pitch % 4 == 0;
+    const dim3 grid = grid_for(w, rows);
+    RGB_DISPATCH(k_rgb_pack, f, grid, s, a);
+}
+
+}  // namespace srcnn
