@@ -4,7 +4,7 @@
 #                      38-39) -- a program linked with -lsrcnn runs on this library without relinking
 #   make install    -> $(DESTDIR)$(PREFIX)/lib/{libsrcnn_amd.so,libsrcnn.so,libsrcnn.a}, include/{libsrcnn.h,srcnn_amd.h}
 #                      (the reference's install / uninstall: Makefiles/Makefile.linux:64-75)
-#   make install-yuv -> the same + include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h (the YUV extensions)
+#   make install-yuv -> the same + include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h, srcnn_amd_yuv_packed.h (the YUV extensions)
 #   make install-rgb -> the same as install + include/srcnn_amd_rgb.h (RGB(A) images in device memory)
 #   make oracle     -> the CPU checker (and oracle/_ref where the reference tree is present)
 #   make test       -> CPU test-suite;  make gpu-test on a gfx950 box
@@ -27,12 +27,12 @@ endif
 HIPFLAGS := --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -fvisibility=hidden -Wall \
             -Wno-unused-result -Wno-unused-value -Wno-ignored-attributes -D__HIP_PLATFORM_AMD__ $(STRICT_DEF)
 ifeq ($(STRICT_ONLY),1)
-SRCS    := srcnn_kernels.hip srcnn_yuv.hip srcnn_yuv16.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_yuv.hip srcnn_yuv16.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 else
-SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv.hip srcnn_yuv16.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv.hip srcnn_yuv16.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 endif
 OBJS    := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(basename $(SRCS))))
-HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
+HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
 
 PREFIX  ?= /usr/local
 ROCM    ?= /opt/rocm
@@ -120,11 +120,12 @@ install: all
 	install -m 644 include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h
 	@if [ -z "$(DESTDIR)" ] && [ "$$(id -u)" = 0 ]; then ldconfig; fi
 
-# the YUV extension headers (include/srcnn_amd_yuv.h, include/srcnn_amd_yuv_ex.h) beside the stable one; `install` keeps the layout of the
+# the YUV extension headers (include/srcnn_amd_yuv.h, include/srcnn_amd_yuv_ex.h, include/srcnn_amd_yuv_packed.h) beside the stable one; `install` keeps the layout of the
 # reference's install target
 install-yuv: install
 	install -m 644 include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h
 	install -m 644 include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h
+	install -m 644 include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h
 
 # the device-resident RGB(A) extension header (include/srcnn_amd_rgb.h)
 install-rgb: install
@@ -132,7 +133,7 @@ install-rgb: install
 
 uninstall:
 	rm -f $(DESTDIR)$(PREFIX)/lib/libsrcnn_amd.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.a
-	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h
+	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h
 	@if [ -z "$(DESTDIR)" ] && [ "$$(id -u)" = 0 ]; then ldconfig; fi
 
 clean:

@@ -53,7 +53,9 @@ YUV_SYMBOLS = ["srcnn_yuv_abi_version", "srcnn_yuv420_upscale_dev"]
 YUV_EX_SYMBOLS = ["srcnn_yuv_ex_abi_version", "srcnn_yuv_plane_size", "srcnn_yuv_upscale_dev"]
 # RGB(A) images already in device memory (include/srcnn_amd_rgb.h, listed in include/srcnn_amd_rgb.abi; its own version)
 RGB_SYMBOLS = ["srcnn_rgb_abi_version", "srcnn_rgb_plane_size", "srcnn_rgb_upscale_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS   # everything the library exports besides the two C++ symbols
+# packed YUV frames (include/srcnn_amd_yuv_packed.h, listed in include/srcnn_amd_yuv_packed.abi; its own version)
+YUV_PACKED_SYMBOLS = ["srcnn_yuv_packed_abi_version", "srcnn_yuv_packed_row_bytes", "srcnn_yuv_packed_upscale_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -146,9 +148,12 @@ def lib():
             "srcnn_rgb_abi_version": (i, []),
             "srcnn_rgb_plane_size": (i, [C.POINTER(RgbFormat), u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(sz)]),
             "srcnn_rgb_upscale_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), vp, sz, vp]),
+            "srcnn_yuv_packed_abi_version": (i, []),
+            "srcnn_yuv_packed_row_bytes": (i, [i, u, C.POINTER(sz), C.POINTER(u)]),
+            "srcnn_yuv_packed_upscale_dev": (i, [i, u, u, f, i, vp, sz, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -602,6 +607,51 @@ def yuv_upscale(planes, layout="planar", chroma="420", depth=8, msb_aligned=Fals
     else:
         check(lib().srcnn_stream_sync(stream))
     return tuple(b.to_numpy(dt, s) for b, s in zip(dout, shapes))
+
+
+(YUVP_YUY2, YUVP_UYVY, YUVP_YVYU, YUVP_Y210, YUVP_Y212, YUVP_Y216, YUVP_VUYA, YUVP_Y410, YUVP_Y416, YUVP_V210) = range(10)
+_YUVP_FORMATS = {"yuy2": YUVP_YUY2, "uyvy": YUVP_UYVY, "yvyu": YUVP_YVYU, "y210": YUVP_Y210, "y212": YUVP_Y212, "y216": YUVP_Y216,
+                 "vuya": YUVP_VUYA, "ayuv": YUVP_VUYA, "y410": YUVP_Y410, "y416": YUVP_Y416, "v210": YUVP_V210}
+
+
+def _yuvp_format(fmt):
+    return int(_YUVP_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else fmt)
+
+
+def yuv_packed_row_bytes(fmt, w):
+    """(tight row bytes, alignment of base and pitch) of a w-pixel row of a packed format: a YUVP_* value or its name
+    ("yuy2", "v210" ...; srcnn_yuv_packed_row_bytes; no device)."""
+    rb, al = C.c_size_t(0), C.c_uint(0)
+    check(lib().srcnn_yuv_packed_row_bytes(_yuvp_format(fmt), int(w), C.byref(rb), C.byref(al)))
+    return rb.value, al.value
+
+
+def yuv_packed_upscale_dev(fmt, w, h, multiply, filt, src, src_pitch, dst, dst_pitch, stream=None):
+    """srcnn_yuv_packed_upscale_dev on device memory, as given: src / dst one frame argument each (see _addr), pitches in
+    bytes (0 = tight).  Asynchronous on `stream` (a Stream, a raw handle or None); raises SrcnnError with the library's code."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_yuv_packed_upscale_dev(_yuvp_format(fmt), int(w), int(h), float(np.float32(multiply)), int(filt), _addr(src),
+                                             int(src_pitch or 0), _addr(dst), int(dst_pitch or 0), handle))
+
+
+def yuv_packed_upscale(frame, fmt, w, multiply=2.0, filt=SRCNNF_Bicubic, stream=None):
+    """One packed YUV frame through srcnn_yuv_packed_upscale_dev: a 2-D uint8 array of h x row_bytes(w) in, one of
+    dh x row_bytes(dw) out (tight rows; `w` says how many pixels a row holds)."""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    rb, _ = yuv_packed_row_bytes(fmt, w)
+    if frame.ndim != 2 or frame.shape[1] != rb:
+        raise ValueError("a %d-pixel row of this format has %d bytes: the frame is %r" % (w, rb, frame.shape))
+    h = frame.shape[0]
+    dw, dh = output_size(w, h, multiply)
+    drb, _ = yuv_packed_row_bytes(fmt, dw)
+    din = DeviceBuffer.from_numpy(frame)
+    dout = DeviceBuffer(max(1, dh * drb))
+    yuv_packed_upscale_dev(fmt, w, h, multiply, filt, din, 0, dout, 0, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    return dout.to_numpy(np.uint8, (dh, drb))
 
 
 RGB_INTERLEAVED, RGB_PLANAR = 0, 1

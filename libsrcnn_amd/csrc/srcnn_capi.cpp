@@ -30,6 +30,7 @@
 #include "srcnn_rgb.h"
 #include "../../include/srcnn_amd_yuv.h"
 #include "../../include/srcnn_amd_yuv_ex.h"
+#include "../../include/srcnn_amd_yuv_packed.h"
 #include "../../include/srcnn_amd_rgb.h"
 
 namespace srcnn {
@@ -1312,6 +1313,125 @@ int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, un
     return SRCNN_OK;
 }
 
+// ---- packed YUV frames (include/srcnn_amd_yuv_packed.h) ----
+
+// What a packed format comes down to: the kernels' rule, chroma subsampling, bytes of a row and the alignment of base and pitch.
+struct YuvPackedGeom {
+    YuvPackedRule rule;
+    unsigned sx = 1;         // chroma columns = ceil(w / 2^sx); chroma rows = luma rows in every packed format
+    bool alpha = false;
+    unsigned align = 1;
+    unsigned ccols(unsigned w) const { return (w + sx) >> sx; }
+    size_t row_bytes(unsigned w) const
+    {
+        switch (rule.kind) {
+        case kPk422x8: return (size_t)4 * ((w + 1) / 2);
+        case kPk422x16: return (size_t)8 * ((w + 1) / 2);
+        case kPk444x8:
+        case kPk410: return (size_t)4 * w;
+        case kPk444x16: return (size_t)8 * w;
+        default: return (size_t)128 * ((w + 47) / 48);
+        }
+    }
+};
+
+// SRCNN_YUVP_* -> YuvPackedGeom, or SRCNN_E_ARG
+int yuv_packed_geom(int format, YuvPackedGeom& g)
+{
+    // kind, depth of Y / U / V, depth of alpha (0: none), alignment, bit positions of (Y0 U Y1 V) or (Y U V A) in an 8-bit dword
+    static const struct { int kind; unsigned depth, adepth, align, sh[4]; } T[] = {
+        /* SRCNN_YUVP_YUY2 */ {kPk422x8, 8, 0, 1, {0, 8, 16, 24}},
+        /* SRCNN_YUVP_UYVY */ {kPk422x8, 8, 0, 1, {8, 0, 24, 16}},
+        /* SRCNN_YUVP_YVYU */ {kPk422x8, 8, 0, 1, {0, 24, 16, 8}},
+        /* SRCNN_YUVP_Y210 */ {kPk422x16, 10, 0, 2, {0, 0, 0, 0}},
+        /* SRCNN_YUVP_Y212 */ {kPk422x16, 12, 0, 2, {0, 0, 0, 0}},
+        /* SRCNN_YUVP_Y216 */ {kPk422x16, 16, 0, 2, {0, 0, 0, 0}},
+        /* SRCNN_YUVP_VUYA */ {kPk444x8, 8, 8, 1, {16, 8, 0, 24}},
+        /* SRCNN_YUVP_Y410 */ {kPk410, 10, 2, 4, {0, 0, 0, 0}},
+        /* SRCNN_YUVP_Y416 */ {kPk444x16, 16, 16, 2, {0, 0, 0, 0}},
+        /* SRCNN_YUVP_V210 */ {kPkV210, 10, 0, 4, {0, 0, 0, 0}},
+    };
+    static_assert(SRCNN_YUVP_YUY2 == 0 && SRCNN_YUVP_V210 == 9 && sizeof(T) / sizeof(T[0]) == 10, "the table is indexed by SRCNN_YUVP_*");
+    if (format < 0 || format > SRCNN_YUVP_V210) return fail(SRCNN_E_ARG, "unknown packed YUV format %d", format);
+    const auto& t = T[format];
+    g.rule.kind = t.kind;
+    for (int k = 0; k < 4; ++k) g.rule.sh[k] = t.sh[k];
+    g.rule.shift = t.kind == kPk422x16 ? 16u - t.depth : 0u;
+    g.rule.mask = (1u << t.depth) - 1u;
+    g.rule.amask = t.adepth ? (1u << t.adepth) - 1u : 0u;
+    g.rule.up = (float)(1u << (t.depth - 8));
+    g.rule.down = 1.f / g.rule.up;
+    g.sx = (t.kind == kPk422x8 || t.kind == kPk422x16 || t.kind == kPkV210) ? 1 : 0;
+    g.alpha = t.adepth != 0;
+    g.align = t.align;
+    return SRCNN_OK;
+}
+
+// Everything srcnn_yuv_packed_upscale_dev refuses beyond the format itself, checked before any device lookup.
+int check_yuv_packed_args(const YuvPackedGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* src,
+                          size_t src_pitch, void* dst, size_t dst_pitch, unsigned& dw, unsigned& dh, YuvPlane& in, YuvPlane& out)
+{
+    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL frame");
+    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
+    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
+    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
+        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
+    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
+    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
+        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
+    for (int side = 0; side < 2; ++side) {
+        YuvPlane& p = side ? out : in;
+        const size_t pitch = side ? dst_pitch : src_pitch;
+        p.lo = static_cast<const unsigned char*>(side ? dst : src);
+        p.row_bytes = g.row_bytes(side ? dw : w);
+        p.rows = side ? dh : h;
+        p.pitch = pitch ? pitch : p.row_bytes;
+        if (p.pitch < p.row_bytes)
+            return fail(SRCNN_E_ARG, "%s pitch %zu is below the row of %zu bytes", side ? "output" : "input", p.pitch, p.row_bytes);
+        if ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & (g.align - 1))
+            return fail(SRCNN_E_ARG, "%s frame: base address and pitch must be multiples of %u", side ? "output" : "input", g.align);
+    }
+    if (overlaps(in, out)) return fail(SRCNN_E_ARG, "input and output frames overlap");
+    return SRCNN_OK;
+}
+
+// unpack -> chroma / alpha resample (whole planes) -> Y' band by band: Y path into a float band, then pack that band with the
+// same rows of the finished chroma and alpha planes (a packed row mixes them, and every packed format has one chroma row per
+// luma row).
+int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                     const YuvPlane& in, const YuvPlane& out)
+{
+    Workspace& ws = *c.ws;
+    const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels):
+    // [Y U V (A) at source size] [U' V' (A') at output size] [Y' of one band]
+    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    const size_t n_y = up64((size_t)w * h), n_c = up64((size_t)cw * h), n_a = g.alpha ? n_y : 0;
+    const size_t m_c = up64((size_t)dcw * dh), m_a = g.alpha ? up64((size_t)dw * dh) : 0;
+    const size_t o_u = n_y, o_v = o_u + n_c, o_a = o_v + n_c, o_cu = o_a + n_a, o_cv = o_cu + m_c, o_ca = o_cv + m_c, o_y = o_ca + m_a;
+    int rc;
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, o_y + (size_t)dw * band))) return rc;
+    float* P = ws.planes;
+    launch_yuvp_unpack(in.lo, in.pitch, w, h, g.rule, P, P + o_u, P + o_v, g.alpha ? P + o_a : nullptr, c.s);
+    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
+    if ((rc = resample_rows_range(c, P + o_u, cw, h, dcw, dh, cfilter, 0, dh, P + o_cu))) return rc;
+    if ((rc = resample_rows_range(c, P + o_v, cw, h, dcw, dh, cfilter, 0, dh, P + o_cv))) return rc;
+    if (g.alpha && (rc = resample_rows_range(c, P + o_a, w, h, dw, dh, cfilter, 0, dh, P + o_ca))) return rc;
+    const YSource ysrc = YSource::from_plane(P);
+    unsigned char* d = const_cast<unsigned char*>(out.lo);
+    for (unsigned a = 0; a < dh; a += band) {
+        const unsigned b = std::min(dh, a + band);
+        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, P + o_y))) return rc;
+        launch_yuvp_pack(P + o_y, P + o_cu + (size_t)a * dcw, P + o_cv + (size_t)a * dcw, g.alpha ? P + o_ca + (size_t)a * dw : nullptr,
+                         dw, b - a, g.rule, d, out.pitch, a, c.s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 // ---- RGB(A) images (include/srcnn_amd_rgb.h) ----
 
 // srcnn_rgb_format -> RgbRule, or SRCNN_E_ARG
@@ -2089,6 +2209,35 @@ int srcnn_yuv_upscale_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, f
     if (sc.rc) return sc.rc;
     TraceRange tr("srcnn yuv %ux%u -> %ux%u", w, h, dw, dh);
     return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- packed YUV frames (include/srcnn_amd_yuv_packed.h) ----
+int srcnn_yuv_packed_abi_version(void) { return SRCNN_AMD_YUV_PACKED_VERSION; }
+
+int srcnn_yuv_packed_row_bytes(int format, unsigned w, size_t* row_bytes, unsigned* alignment)
+{
+    YuvPackedGeom g;
+    int rc;
+    if ((rc = yuv_packed_geom(format, g))) return rc;
+    if (w == 0) return fail(SRCNN_E_ARG, "zero width");
+    if (row_bytes) *row_bytes = g.row_bytes(w);
+    if (alignment) *alignment = g.align;
+    return SRCNN_OK;
+}
+
+int srcnn_yuv_packed_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter, const void* src, size_t src_pitch,
+                                 void* dst, size_t dst_pitch, void* stream)
+{
+    YuvPackedGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in, out;
+    int rc;
+    if ((rc = yuv_packed_geom(format, g))) return rc;
+    if ((rc = check_yuv_packed_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv packed %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv_packed_frame(sc.c, g, w, h, dw, dh, filter, in, out);
 }
 
 // ---- RGB(A) images in device memory (include/srcnn_amd_rgb.h) ----

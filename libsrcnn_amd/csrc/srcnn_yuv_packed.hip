@@ -1,0 +1,380 @@
+// srcnn_yuv_packed.hip -- the conversions around the SRCNN path for PACKED YUV frames (include/srcnn_amd_yuv_packed.h): one
+// plane whose rows interleave Y, U, V and, for the 4:4:4 formats, alpha.
+//
+//   k_yuvp_unpack   pitched packed rows -> tight float32 planes Y, U, V (A)
+//                   Y = (float)field * 2^-s; U, V, A = (float)field (all exact in fp32).  Only the bits of a field are read.
+//   k_yuvp_pack     tight float32 rows Y' (one band), U', V' (A') (the same rows of the finished planes) -> pitched packed rows
+//                   Y':         (unsigned) (v * 2^s)              layer 3 already clamps v to [0, 255]
+//                   U', V', A': MIN(maxv), MAX(0), truncation      the reference's macro forms on the native scale
+//                   every byte of the tight rows is written once; slots that carry no sample are written as zero
+//
+// Six memory layouts (YuvPackedKind) carry the ten public formats; byte positions, shift, maxv and scale are kernel
+// arguments.  Both kernels are memory-bound.  One lane owns one 16-byte chunk of a packed row -- 8 YUY2 pixels, 4 Y210 /
+// VUYA / Y410 pixels, 2 Y416 pixels or one v210 group of 6 -- and consecutive lanes own consecutive chunks, so a wave reads
+// or writes 1 KiB of packed data in one instruction where base and pitch are 16-byte aligned (decided once per launch).
+// Misaligned frames and a row's last partial chunk move their dwords one by one, in pieces of the alignment the frame has
+// (4, 2 or 1 bytes).  The float side uses float4 / float2 where the row length keeps every row start aligned for it (again
+// once per launch), else scalars.
+//
+// v210: a group's 6 luma floats start at 24 * group bytes, which no float4 store can take at every group.  The mapping stays
+// lane = group: a lane moves its 6 Y as three float2 (8-byte aligned whenever w is even) and its 3 + 3 chroma as dwords.
+// The 64 lanes of a wave then cover ONE contiguous span of 1536 B of Y and 768 B of each chroma plane, so every cache
+// line of the planes is still written in full by one instruction group; giving a lane two groups for float4 stores would
+// stride the packed side by 32 B instead and halve the 16-byte coalescing there.  In the pack kernel the groups that only
+// pad a row to its 128-byte block are chunks like any other, with no valid sample: they are written as zero.
+//
+// Grid-stride over rows x chunks.  The host side is srcnn_capi.cpp (srcnn_yuv_packed_upscale_dev); planar and semi-planar
+// frames are srcnn_yuv.hip and srcnn_yuv16.hip.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "srcnn_yuv.h"
+
+#pragma clang fp contract(off)
+
+namespace srcnn {
+
+namespace {
+
+// samples of Y, of each chroma plane and of alpha in one 16-byte chunk
+template <int K> struct PkShape;
+template <> struct PkShape<kPk422x8>  { static constexpr unsigned NY = 8, NC = 4, NA = 0; };
+template <> struct PkShape<kPk422x16> { static constexpr unsigned NY = 4, NC = 2, NA = 0; };
+template <> struct PkShape<kPk444x8>  { static constexpr unsigned NY = 4, NC = 4, NA = 4; };
+template <> struct PkShape<kPk410>    { static constexpr unsigned NY = 4, NC = 4, NA = 4; };
+template <> struct PkShape<kPk444x16> { static constexpr unsigned NY = 2, NC = 2, NA = 2; };
+template <> struct PkShape<kPkV210>   { static constexpr unsigned NY = 6, NC = 3, NA = 0; };
+
+// how the packed side of a launch is addressed: 16-byte vectors, or pieces of 4, 2 or 1 bytes
+enum { kIoVec = 0, kIoDword = 4, kIoWord = 2, kIoByte = 1 };
+
+template <bool SAT>
+__device__ __forceinline__ unsigned to_word(float v, float scale, float maxv)
+{
+    if constexpr (SAT) {                 // MIN(maxv, v) then MAX(0.f, .) then truncating cast, in the reference's macro forms
+        v = (maxv < v) ? maxv : v;
+        v = (0.f > v) ? 0.f : v;
+        return (unsigned)v;
+    } else {
+        return (unsigned)(v * scale);
+    }
+}
+
+__device__ __forceinline__ unsigned load_dword(const unsigned char* p, int io)
+{
+    if (io == kIoByte) return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+    if (io == kIoWord) {
+        const unsigned short* ps = reinterpret_cast<const unsigned short*>(p);
+        return (unsigned)ps[0] | ((unsigned)ps[1] << 16);
+    }
+    return *reinterpret_cast<const unsigned*>(p);
+}
+
+__device__ __forceinline__ void store_dword(unsigned char* p, unsigned v, int io)
+{
+    if (io == kIoByte) {
+        p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24);
+    } else if (io == kIoWord) {
+        unsigned short* ps = reinterpret_cast<unsigned short*>(p);
+        ps[0] = (unsigned short)v; ps[1] = (unsigned short)(v >> 16);
+    } else {
+        *reinterpret_cast<unsigned*>(p) = v;
+    }
+}
+
+// N floats at p, the first n of them valid: vector accesses for a whole piece where the launch allows them
+template <unsigned N>
+__device__ __forceinline__ void store_floats(float* p, const float* v, unsigned n, int vec)
+{
+    if constexpr (N == 0) return;
+    if (vec && n == N && N % 2 == 0) {
+        if constexpr (N % 4 == 0) {
+#pragma unroll
+            for (unsigned k = 0; k < N; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+        } else if constexpr (N % 2 == 0) {
+#pragma unroll
+            for (unsigned k = 0; k < N; k += 2) *reinterpret_cast<float2*>(p + k) = make_float2(v[k], v[k + 1]);
+        }
+    } else {
+#pragma unroll
+        for (unsigned k = 0; k < N; ++k)
+            if (k < n) p[k] = v[k];
+    }
+}
+
+template <unsigned N>
+__device__ __forceinline__ void load_floats(const float* p, float* v, unsigned n, int vec)
+{
+    if constexpr (N == 0) return;
+    if (vec && n == N && N % 2 == 0) {
+        if constexpr (N % 4 == 0) {
+#pragma unroll
+            for (unsigned k = 0; k < N; k += 4) {
+                const float4 x = *reinterpret_cast<const float4*>(p + k);
+                v[k] = x.x; v[k + 1] = x.y; v[k + 2] = x.z; v[k + 3] = x.w;
+            }
+        } else if constexpr (N % 2 == 0) {
+#pragma unroll
+            for (unsigned k = 0; k < N; k += 2) {
+                const float2 x = *reinterpret_cast<const float2*>(p + k);
+                v[k] = x.x; v[k + 1] = x.y;
+            }
+        }
+    } else {
+#pragma unroll
+        for (unsigned k = 0; k < N; ++k) v[k] = k < n ? p[k] : 0.f;
+    }
+}
+
+// the four dwords of a chunk -> field values (every slot of the chunk, valid or not)
+template <int K>
+__device__ __forceinline__ void decode(const unsigned q[4], const YuvPackedRule& f, unsigned* y, unsigned* u, unsigned* v, unsigned* a)
+{
+    if constexpr (K == kPk422x8) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) {
+            y[2 * j] = (q[j] >> f.sh[0]) & 0xffu; u[j] = (q[j] >> f.sh[1]) & 0xffu;
+            y[2 * j + 1] = (q[j] >> f.sh[2]) & 0xffu; v[j] = (q[j] >> f.sh[3]) & 0xffu;
+        }
+    } else if constexpr (K == kPk422x16) {
+#pragma unroll
+        for (unsigned j = 0; j < 2; ++j) {
+            y[2 * j] = ((q[2 * j] & 0xffffu) >> f.shift) & f.mask; u[j] = ((q[2 * j] >> 16) >> f.shift) & f.mask;
+            y[2 * j + 1] = ((q[2 * j + 1] & 0xffffu) >> f.shift) & f.mask; v[j] = ((q[2 * j + 1] >> 16) >> f.shift) & f.mask;
+        }
+    } else if constexpr (K == kPk444x8) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) {
+            y[j] = (q[j] >> f.sh[0]) & 0xffu; u[j] = (q[j] >> f.sh[1]) & 0xffu;
+            v[j] = (q[j] >> f.sh[2]) & 0xffu; a[j] = (q[j] >> f.sh[3]) & 0xffu;
+        }
+    } else if constexpr (K == kPk410) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) {
+            u[j] = q[j] & 0x3ffu; y[j] = (q[j] >> 10) & 0x3ffu; v[j] = (q[j] >> 20) & 0x3ffu; a[j] = q[j] >> 30;
+        }
+    } else if constexpr (K == kPk444x16) {
+#pragma unroll
+        for (unsigned j = 0; j < 2; ++j) {
+            u[j] = q[2 * j] & 0xffffu; y[j] = q[2 * j] >> 16; v[j] = q[2 * j + 1] & 0xffffu; a[j] = q[2 * j + 1] >> 16;
+        }
+    } else {                             // v210: Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5
+        u[0] = q[0] & 0x3ffu; y[0] = (q[0] >> 10) & 0x3ffu; v[0] = (q[0] >> 20) & 0x3ffu;
+        y[1] = q[1] & 0x3ffu; u[1] = (q[1] >> 10) & 0x3ffu; y[2] = (q[1] >> 20) & 0x3ffu;
+        v[1] = q[2] & 0x3ffu; y[3] = (q[2] >> 10) & 0x3ffu; u[2] = (q[2] >> 20) & 0x3ffu;
+        y[4] = q[3] & 0x3ffu; v[2] = (q[3] >> 10) & 0x3ffu; y[5] = (q[3] >> 20) & 0x3ffu;
+    }
+}
+
+// field values (already inside their fields' ranges; zero where the slot carries no sample) -> the four dwords of a chunk
+template <int K>
+__device__ __forceinline__ void encode(const unsigned* y, const unsigned* u, const unsigned* v, const unsigned* a, const YuvPackedRule& f, unsigned q[4])
+{
+    if constexpr (K == kPk422x8) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) q[j] = (y[2 * j] << f.sh[0]) | (u[j] << f.sh[1]) | (y[2 * j + 1] << f.sh[2]) | (v[j] << f.sh[3]);
+    } else if constexpr (K == kPk422x16) {
+#pragma unroll
+        for (unsigned j = 0; j < 2; ++j) {
+            q[2 * j] = (y[2 * j] << f.shift) | (u[j] << (16 + f.shift));
+            q[2 * j + 1] = (y[2 * j + 1] << f.shift) | (v[j] << (16 + f.shift));
+        }
+    } else if constexpr (K == kPk444x8) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) q[j] = (y[j] << f.sh[0]) | (u[j] << f.sh[1]) | (v[j] << f.sh[2]) | (a[j] << f.sh[3]);
+    } else if constexpr (K == kPk410) {
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) q[j] = u[j] | (y[j] << 10) | (v[j] << 20) | (a[j] << 30);
+    } else if constexpr (K == kPk444x16) {
+#pragma unroll
+        for (unsigned j = 0; j < 2; ++j) {
+            q[2 * j] = u[j] | (y[j] << 16);
+            q[2 * j + 1] = v[j] | (a[j] << 16);
+        }
+    } else {
+        q[0] = u[0] | (y[0] << 10) | (v[0] << 20);
+        q[1] = y[1] | (u[1] << 10) | (y[2] << 20);
+        q[2] = v[1] | (y[3] << 10) | (u[2] << 20);
+        q[3] = y[4] | (v[2] << 10) | (y[5] << 20);
+    }
+}
+
+__device__ __forceinline__ unsigned valid_of(unsigned per_chunk, unsigned chunk, unsigned have)
+{
+    const unsigned first = per_chunk * chunk;
+    return first >= have ? 0u : min(per_chunk, have - first);
+}
+
+// cpr: 16-byte chunks of a row that carry a sample; row_dwords: dwords of a tight row; cw: chroma samples of a row.
+// io: kIo* of the packed side; fvec: vector accesses on the float side.
+template <int K>
+__global__ __launch_bounds__(256) void k_yuvp_unpack(const unsigned char* __restrict__ src, size_t pitch, unsigned w, unsigned cw,
+                                                     unsigned rows, unsigned cpr, unsigned row_dwords, float* __restrict__ dy,
+                                                     float* __restrict__ du, float* __restrict__ dv, float* __restrict__ da,
+                                                     YuvPackedRule f, int io, int fvec)
+{
+    using S = PkShape<K>;
+    const unsigned total = cpr * rows;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned r = i / cpr, c = i - r * cpr;
+        const unsigned nd = min(4u, row_dwords - 4 * c);
+        const unsigned char* p = src + (size_t)r * pitch + (size_t)16 * c;
+        unsigned q[4] = {0, 0, 0, 0};
+        if (nd == 4 && io == kIoVec) {
+            const uint4 x = *reinterpret_cast<const uint4*>(p);
+            q[0] = x.x; q[1] = x.y; q[2] = x.z; q[3] = x.w;
+        } else {
+            const int piece = io == kIoVec ? kIoDword : io;
+#pragma unroll
+            for (unsigned j = 0; j < 4; ++j)
+                if (j < nd) q[j] = load_dword(p + 4 * j, piece);
+        }
+        unsigned y[8], u[4], v[4], a[4];
+        decode<K>(q, f, y, u, v, a);
+        float fy[8], fu[4], fv[4], fa[4];
+#pragma unroll
+        for (unsigned k = 0; k < S::NY; ++k) fy[k] = (float)y[k] * f.down;
+#pragma unroll
+        for (unsigned k = 0; k < S::NC; ++k) { fu[k] = (float)u[k]; fv[k] = (float)v[k]; }
+#pragma unroll
+        for (unsigned k = 0; k < S::NA; ++k) fa[k] = (float)a[k];
+        const unsigned ny = valid_of(S::NY, c, w), nc = valid_of(S::NC, c, cw);
+        store_floats<S::NY>(dy + (size_t)r * w + (size_t)S::NY * c, fy, ny, fvec);
+        store_floats<S::NC>(du + (size_t)r * cw + (size_t)S::NC * c, fu, nc, fvec);
+        store_floats<S::NC>(dv + (size_t)r * cw + (size_t)S::NC * c, fv, nc, fvec);
+        if constexpr (S::NA > 0) store_floats<S::NA>(da + (size_t)r * w + (size_t)S::NA * c, fa, ny, fvec);
+    }
+}
+
+// cpr: 16-byte chunks of a tight row (v210: its padding groups included).  Source row r of every plane goes to destination
+// row row0 + r.
+template <int K>
+__global__ __launch_bounds__(256) void k_yuvp_pack(const float* __restrict__ sy, const float* __restrict__ su,
+                                                   const float* __restrict__ sv, const float* __restrict__ sa, unsigned w,
+                                                   unsigned cw, unsigned rows, unsigned cpr, unsigned row_dwords,
+                                                   unsigned char* __restrict__ dst, size_t pitch, unsigned row0, YuvPackedRule f,
+                                                   int io, int fvec)
+{
+    using S = PkShape<K>;
+    const unsigned total = cpr * rows;
+    const float maxv = (float)f.mask, amax = (float)f.amask;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const unsigned r = i / cpr, c = i - r * cpr;
+        const unsigned nd = min(4u, row_dwords - 4 * c);
+        const unsigned ny = valid_of(S::NY, c, w), nc = valid_of(S::NC, c, cw);
+        float fy[8], fu[4], fv[4], fa[4];
+        load_floats<S::NY>(sy + (size_t)r * w + (size_t)S::NY * c, fy, ny, fvec);
+        load_floats<S::NC>(su + (size_t)r * cw + (size_t)S::NC * c, fu, nc, fvec);
+        load_floats<S::NC>(sv + (size_t)r * cw + (size_t)S::NC * c, fv, nc, fvec);
+        if constexpr (S::NA > 0) load_floats<S::NA>(sa + (size_t)r * w + (size_t)S::NA * c, fa, ny, fvec);
+        unsigned y[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0}, a[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (unsigned k = 0; k < S::NY; ++k) y[k] = k < ny ? to_word<false>(fy[k], f.up, maxv) : 0u;
+#pragma unroll
+        for (unsigned k = 0; k < S::NC; ++k) {
+            u[k] = k < nc ? to_word<true>(fu[k], 1.f, maxv) : 0u;
+            v[k] = k < nc ? to_word<true>(fv[k], 1.f, maxv) : 0u;
+        }
+#pragma unroll
+        for (unsigned k = 0; k < S::NA; ++k) a[k] = k < ny ? to_word<true>(fa[k], 1.f, amax) : 0u;
+        unsigned q[4];
+        encode<K>(y, u, v, a, f, q);
+        unsigned char* p = dst + (size_t)(row0 + r) * pitch + (size_t)16 * c;
+        if (nd == 4 && io == kIoVec) {
+            *reinterpret_cast<uint4*>(p) = make_uint4(q[0], q[1], q[2], q[3]);
+        } else {
+            const int piece = io == kIoVec ? kIoDword : io;
+#pragma unroll
+            for (unsigned j = 0; j < 4; ++j)
+                if (j < nd) store_dword(p + 4 * j, q[j], piece);
+        }
+    }
+}
+
+inline bool aligned_to(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int io_of(const void* base, size_t pitch)
+{
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(base) | (uintptr_t)pitch;
+    return bits % 16 == 0 ? kIoVec : bits % 4 == 0 ? kIoDword : bits % 2 == 0 ? kIoWord : kIoByte;
+}
+
+// The row length that keeps every row start of every float plane aligned for the widest access its kind uses (float4 for 8
+// and 4 samples, float2 for 6 and 2; 3 samples go one by one).
+bool float_vec_ok(int kind, unsigned w)
+{
+    switch (kind) {
+    case kPk422x8: return w % 8 == 0;    // Y: float4 at 8 per chunk; chroma w / 2 per row, float4
+    case kPk422x16: return w % 4 == 0;   // Y: float4; chroma w / 2 per row, float2
+    case kPk444x8:
+    case kPk410: return w % 4 == 0;
+    default: return w % 2 == 0;          // Y416: float2;  v210: float2 for Y
+    }
+}
+
+dim3 grid_for(size_t total) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 4096))); }
+
+// tight bytes of a w-pixel row (srcnn_yuv_packed_row_bytes): always whole dwords
+size_t row_bytes_of(int kind, unsigned w)
+{
+    switch (kind) {
+    case kPk422x8: return (size_t)4 * ((w + 1) / 2);
+    case kPk422x16: return (size_t)8 * ((w + 1) / 2);
+    case kPk444x8:
+    case kPk410: return (size_t)4 * w;
+    case kPk444x16: return (size_t)8 * w;
+    default: return (size_t)128 * ((w + 47) / 48);
+    }
+}
+
+}  // namespace
+
+void launch_yuvp_unpack(const unsigned char* src, size_t pitch, unsigned w, unsigned rows, const YuvPackedRule& f, float* dy,
+                        float* du, float* dv, float* da, hipStream_t s)
+{
+    const bool sub = f.kind == kPk422x8 || f.kind == kPk422x16 || f.kind == kPkV210;
+    const unsigned cw = sub ? (w + 1) / 2 : w;
+    const size_t rb = row_bytes_of(f.kind, w);
+    const unsigned row_dwords = (unsigned)(rb / 4);
+    const unsigned cpr = f.kind == kPkV210 ? (w + 5) / 6 : (unsigned)((rb + 15) / 16);   // v210: only the groups that carry a sample
+    const int io = io_of(src, pitch);
+    const int fvec = float_vec_ok(f.kind, w) && aligned_to(dy, 16) && aligned_to(du, 16) && aligned_to(dv, 16) && aligned_to(da, 16);
+    const dim3 g = grid_for((size_t)cpr * rows), b(256);
+#define SRCNN_YUVP_UNPACK(K) hipLaunchKernelGGL(k_yuvp_unpack<K>, g, b, 0, s, src, pitch, w, cw, rows, cpr, row_dwords, dy, du, dv, da, f, io, fvec)
+    switch (f.kind) {
+    case kPk422x8: SRCNN_YUVP_UNPACK(kPk422x8); break;
+    case kPk422x16: SRCNN_YUVP_UNPACK(kPk422x16); break;
+    case kPk444x8: SRCNN_YUVP_UNPACK(kPk444x8); break;
+    case kPk410: SRCNN_YUVP_UNPACK(kPk410); break;
+    case kPk444x16: SRCNN_YUVP_UNPACK(kPk444x16); break;
+    default: SRCNN_YUVP_UNPACK(kPkV210); break;
+    }
+#undef SRCNN_YUVP_UNPACK
+}
+
+void launch_yuvp_pack(const float* sy, const float* su, const float* sv, const float* sa, unsigned w, unsigned rows,
+                      const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s)
+{
+    const bool sub = f.kind == kPk422x8 || f.kind == kPk422x16 || f.kind == kPkV210;
+    const unsigned cw = sub ? (w + 1) / 2 : w;
+    const size_t rb = row_bytes_of(f.kind, w);
+    const unsigned row_dwords = (unsigned)(rb / 4);
+    const unsigned cpr = (unsigned)((rb + 15) / 16);                 // every chunk of the tight row, v210's padding groups included
+    const int io = io_of(dst, pitch);
+    const int fvec = float_vec_ok(f.kind, w) && aligned_to(sy, 16) && aligned_to(su, 16) && aligned_to(sv, 16) && aligned_to(sa, 16);
+    const dim3 g = grid_for((size_t)cpr * rows), b(256);
+#define SRCNN_YUVP_PACK(K) hipLaunchKernelGGL(k_yuvp_pack<K>, g, b, 0, s, sy, su, sv, sa, w, cw, rows, cpr, row_dwords, dst, pitch, row0, f, io, fvec)
+    switch (f.kind) {
+    case kPk422x8: SRCNN_YUVP_PACK(kPk422x8); break;
+    case kPk422x16: SRCNN_YUVP_PACK(kPk422x16); break;
+    case kPk444x8: SRCNN_YUVP_PACK(kPk444x8); break;
+    case kPk410: SRCNN_YUVP_PACK(kPk410); break;
+    case kPk444x16: SRCNN_YUVP_PACK(kPk444x16); break;
+    default: SRCNN_YUVP_PACK(kPkV210); break;
+    }
+#undef SRCNN_YUVP_PACK
+}
+
+}  // namespace srcnn
