@@ -1,6 +1,6 @@
 // srcnn_capi.cpp -- the extern "C" boundary (include/srcnn_amd.h) over the gfx950 kernels: contexts, plumbing and the
 // device-resident hot path.  The host-pointer pipelines (frame stream, ProcessSRCNN surface, node-level calls) are in
-// srcnn_pipeline.cpp; the state both share is srcnn_host.hpp.
+// srcnn_pipeline.cpp, the YUV / RGB frame calls around the Y path in srcnn_frames.cpp; the state all share is srcnn_host.hpp.
 //
 // Host-side orchestration only: argument validation with the reference's return codes
 // (src/libsrcnn.cpp:951-966), lazily built + cached contribution tables
@@ -26,12 +26,6 @@
 #include <unistd.h>
 
 #include "srcnn_host.hpp"
-#include "srcnn_yuv.h"
-#include "srcnn_rgb.h"
-#include "../../include/srcnn_amd_yuv.h"
-#include "../../include/srcnn_amd_yuv_ex.h"
-#include "../../include/srcnn_amd_yuv_packed.h"
-#include "../../include/srcnn_amd_rgb.h"
 
 namespace srcnn {
 
@@ -1097,24 +1091,6 @@ int check_y_path_args(const float* d_in, unsigned w, unsigned h, unsigned dw, un
 
 namespace {
 
-// An eager call on a caller-visible stream: the stream's own scratch, locked while this call enqueues.
-struct StreamCall {
-    std::vector<TableRef> tables;
-    Call c;
-    std::unique_lock<std::mutex> lk;
-    int rc = SRCNN_OK;
-    explicit StreamCall(void* stream)
-    {
-        c.cx = ctx_for_stream(stream);
-        if (!c.cx) { rc = SRCNN_E_NODEVICE; return; }
-        c.s = (hipStream_t)stream;
-        c.ws = workspace_for(*c.cx, c.s);
-        c.mode = G.mode.load();
-        c.hold = &tables;
-        lk = std::unique_lock<std::mutex>(c.ws->mu);
-    }
-};
-
 int batch_frames(Call& c, const float* d_in, unsigned w, unsigned h, unsigned nframes, float* d_out)
 {
     const size_t in_n = (size_t)w * h, out_n = in_n * 4;
@@ -1170,407 +1146,6 @@ void release_context(Ctx& cx)
     cx.clock_buf = nullptr;
     { std::lock_guard<std::mutex> bl(cx.bounce.mu); cx.bounce.release(); }
     { std::lock_guard<std::mutex> hl(cx.host_call.mu); cx.host_call.release(); }
-}
-
-// ---- YUV frames (include/srcnn_amd_yuv.h: 8-bit 4:2:0; include/srcnn_amd_yuv_ex.h: every other format) ----
-
-struct YuvPlane {
-    const unsigned char* lo = nullptr;   // first byte of the plane
-    size_t pitch = 0, row_bytes = 0;
-    unsigned rows = 0;
-    const unsigned char* hi() const { return lo + pitch * (rows - 1) + row_bytes; }   // one past the last byte
-};
-
-bool overlaps(const YuvPlane& a, const YuvPlane& b) { return a.lo < b.hi() && b.lo < a.hi(); }
-
-// What a frame format comes down to for the frame function: plane count, chroma subsampling, sample width, read / write rule.
-struct YuvGeom {
-    bool semi = false;       // Y + interleaved UV (2 planes) instead of Y, U, V
-    unsigned sx = 1, sy = 1; // chroma columns = ceil(w / 2^sx), rows = ceil(h / 2^sy)
-    unsigned bps = 1;        // bytes per sample: 1 (depth 8) or 2
-    Yuv16Rule rule;          // bps == 2
-    unsigned ccols(unsigned w) const { return (w + sx) >> sx; }
-    unsigned crows(unsigned h) const { return (h + sy) >> sy; }
-};
-
-// srcnn_yuv_format -> YuvGeom, or SRCNN_E_ARG
-int yuv_geom_from_format(const srcnn_yuv_format* f, YuvGeom& g)
-{
-    if (!f) return fail(SRCNN_E_ARG, "NULL format");
-    if (f->struct_size != sizeof(srcnn_yuv_format)) return fail(SRCNN_E_ARG, "struct_size %u is not %zu", f->struct_size, sizeof(srcnn_yuv_format));
-    if (f->layout != SRCNN_YUV_PLANAR && f->layout != SRCNN_YUV_SEMIPLANAR) return fail(SRCNN_E_ARG, "unknown YUV layout %d", f->layout);
-    if (f->chroma != SRCNN_YUV_420 && f->chroma != SRCNN_YUV_422 && f->chroma != SRCNN_YUV_444) return fail(SRCNN_E_ARG, "unknown chroma format %d", f->chroma);
-    if (f->depth != 8 && f->depth != 10 && f->depth != 12 && f->depth != 14 && f->depth != 16) return fail(SRCNN_E_ARG, "unsupported depth %d", f->depth);
-    if ((f->msb_aligned != 0 && f->msb_aligned != 1) || (f->depth == 8 && f->msb_aligned)) return fail(SRCNN_E_ARG, "bad msb_aligned %d at depth %d", f->msb_aligned, f->depth);
-    g.semi = f->layout == SRCNN_YUV_SEMIPLANAR;
-    g.sx = f->chroma == SRCNN_YUV_444 ? 0 : 1;
-    g.sy = f->chroma == SRCNN_YUV_420 ? 1 : 0;
-    g.bps = f->depth == 8 ? 1 : 2;
-    if (g.bps == 2) {
-        const unsigned s = (unsigned)f->depth - 8, shift = f->msb_aligned ? 16u - (unsigned)f->depth : 0u;
-        g.rule.rshift = g.rule.lshift = shift;
-        g.rule.mask = (1u << f->depth) - 1u;
-        g.rule.up = (float)(1u << s);
-        g.rule.down = 1.f / g.rule.up;
-    }
-    return SRCNN_OK;
-}
-
-// Everything the YUV frame calls refuse beyond the format itself, checked before any device lookup.
-int check_yuv_args(const YuvGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[3],
-                   const size_t src_pitch[3], void* const dst[3], const size_t dst_pitch[3], unsigned& dw,
-                   unsigned& dh, YuvPlane in[3], YuvPlane out[3])
-{
-    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
-    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    const int np = g.semi ? 2 : 3;
-    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
-    for (int k = 0; k < np; ++k)
-        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
-    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
-    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
-    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
-        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
-    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
-    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
-        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
-    for (int side = 0; side < 2; ++side) {
-        YuvPlane* P = side ? out : in;
-        const unsigned pw = side ? dw : w, ph = side ? dh : h, pcw = g.ccols(pw), pch = g.crows(ph);
-        const size_t* pitch = side ? dst_pitch : src_pitch;
-        for (int k = 0; k < np; ++k) {
-            YuvPlane& p = P[k];
-            p.lo = static_cast<const unsigned char*>(side ? dst[k] : src[k]);
-            p.row_bytes = (size_t)g.bps * (k == 0 ? pw : (g.semi ? 2 * (size_t)pcw : pcw));
-            p.rows = k == 0 ? ph : pch;
-            p.pitch = pitch && pitch[k] ? pitch[k] : p.row_bytes;
-            if (p.pitch < p.row_bytes)
-                return fail(SRCNN_E_ARG, "%s pitch %zu of plane %d is below its row of %zu bytes", side ? "output" : "input", p.pitch, k, p.row_bytes);
-            if (g.bps == 2 && ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & 1))
-                return fail(SRCNN_E_ARG, "%s plane %d: 16-bit samples need an even base address and pitch", side ? "output" : "input", k);
-        }
-    }
-    for (int a = 0; a < np; ++a)
-        for (int b = 0; b < np; ++b)
-            if (overlaps(in[a], out[b])) return fail(SRCNN_E_ARG, "input plane %d overlaps output plane %d", a, b);
-    return SRCNN_OK;
-}
-
-// Rows of Y' one pass of the Y path produces: the whole frame when its layer-2 planes fit the workspace cap (y_path_range's
-// test), else budget_band_rows.
-unsigned yuv_band_rows(const Call& c, unsigned dw, unsigned dh)
-{
-    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
-    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)dh + 4) <= G.ws_budget.load()) return dh;
-    return std::min(dh, budget_band_rows(dw));
-}
-
-// unpack -> chroma resample + pack -> Y' band by band (Y path into a float band, pack into the destination rows).  Depth 8
-// goes through k_yuv_unpack / k_yuv_pack, 16-bit words through k_yuv16_unpack / k_yuv16_pack.
-int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
-              const YuvPlane out[3])
-{
-    Workspace& ws = *c.ws;
-    const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
-    const unsigned band = yuv_band_rows(c, dw, dh);
-    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels)
-    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t o_u = up64((size_t)w * h), o_v = o_u + up64((size_t)cw * ch), o_cu = o_v + up64((size_t)cw * ch);
-    const size_t o_cv = o_cu + up64((size_t)dcw * dch), o_y = o_cv + up64((size_t)dcw * dch), total = o_y + (size_t)dw * band;
-    int rc;
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, total))) return rc;
-    float* P = ws.planes;
-    auto unpack = [&](const YuvPlane& p, unsigned pw, unsigned ph, bool uv, bool luma, float* d0, float* d1) {
-        if (g.bps == 1) launch_yuv_unpack(p.lo, p.pitch, pw, ph, uv, d0, d1, c.s);
-        else launch_yuv16_unpack(p.lo, p.pitch, pw, ph, uv, g.rule, luma, d0, d1, c.s);
-    };
-    auto pack = [&](const float* s0, const float* s1, unsigned pw, unsigned ph, bool sat, const YuvPlane& p, unsigned row0) {
-        unsigned char* d = const_cast<unsigned char*>(p.lo);
-        if (g.bps == 1) launch_yuv_pack(s0, s1, pw, ph, sat, d, p.pitch, row0, c.s);
-        else launch_yuv16_pack(s0, s1, pw, ph, sat, g.rule, d, p.pitch, row0, c.s);
-    };
-    unpack(in[0], w, h, false, true, P, nullptr);
-    if (g.semi) unpack(in[1], cw, ch, true, false, P + o_u, P + o_v);
-    else {
-        unpack(in[1], cw, ch, false, false, P + o_u, nullptr);
-        unpack(in[2], cw, ch, false, false, P + o_v, nullptr);
-    }
-    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
-    if ((rc = resample_rows_range(c, P + o_u, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cu))) return rc;
-    if ((rc = resample_rows_range(c, P + o_v, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cv))) return rc;
-    if (g.semi) pack(P + o_cu, P + o_cv, dcw, dch, true, out[1], 0);
-    else {
-        pack(P + o_cu, nullptr, dcw, dch, true, out[1], 0);
-        pack(P + o_cv, nullptr, dcw, dch, true, out[2], 0);
-    }
-    const YSource ysrc = YSource::from_plane(P);
-    for (unsigned a = 0; a < dh; a += band) {
-        const unsigned b = std::min(dh, a + band);
-        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, P + o_y))) return rc;
-        pack(P + o_y, nullptr, dw, b - a, false, out[0], a);
-    }
-    HIP_TRY(hipGetLastError());
-    return SRCNN_OK;
-}
-
-// ---- packed YUV frames (include/srcnn_amd_yuv_packed.h) ----
-
-// What a packed format comes down to: the kernels' rule, chroma subsampling, bytes of a row and the alignment of base and pitch.
-struct YuvPackedGeom {
-    YuvPackedRule rule;
-    unsigned sx = 1;         // chroma columns = ceil(w / 2^sx); chroma rows = luma rows in every packed format
-    bool alpha = false;
-    unsigned align = 1;
-    unsigned ccols(unsigned w) const { return (w + sx) >> sx; }
-    size_t row_bytes(unsigned w) const
-    {
-        switch (rule.kind) {
-        case kPk422x8: return (size_t)4 * ((w + 1) / 2);
-        case kPk422x16: return (size_t)8 * ((w + 1) / 2);
-        case kPk444x8:
-        case kPk410: return (size_t)4 * w;
-        case kPk444x16: return (size_t)8 * w;
-        default: return (size_t)128 * ((w + 47) / 48);
-        }
-    }
-};
-
-// SRCNN_YUVP_* -> YuvPackedGeom, or SRCNN_E_ARG
-int yuv_packed_geom(int format, YuvPackedGeom& g)
-{
-    // kind, depth of Y / U / V, depth of alpha (0: none), alignment, bit positions of (Y0 U Y1 V) or (Y U V A) in an 8-bit dword
-    static const struct { int kind; unsigned depth, adepth, align, sh[4]; } T[] = {
-        /* SRCNN_YUVP_YUY2 */ {kPk422x8, 8, 0, 1, {0, 8, 16, 24}},
-        /* SRCNN_YUVP_UYVY */ {kPk422x8, 8, 0, 1, {8, 0, 24, 16}},
-        /* SRCNN_YUVP_YVYU */ {kPk422x8, 8, 0, 1, {0, 24, 16, 8}},
-        /* SRCNN_YUVP_Y210 */ {kPk422x16, 10, 0, 2, {0, 0, 0, 0}},
-        /* SRCNN_YUVP_Y212 */ {kPk422x16, 12, 0, 2, {0, 0, 0, 0}},
-        /* SRCNN_YUVP_Y216 */ {kPk422x16, 16, 0, 2, {0, 0, 0, 0}},
-        /* SRCNN_YUVP_VUYA */ {kPk444x8, 8, 8, 1, {16, 8, 0, 24}},
-        /* SRCNN_YUVP_Y410 */ {kPk410, 10, 2, 4, {0, 0, 0, 0}},
-        /* SRCNN_YUVP_Y416 */ {kPk444x16, 16, 16, 2, {0, 0, 0, 0}},
-        /* SRCNN_YUVP_V210 */ {kPkV210, 10, 0, 4, {0, 0, 0, 0}},
-    };
-    static_assert(SRCNN_YUVP_YUY2 == 0 && SRCNN_YUVP_V210 == 9 && sizeof(T) / sizeof(T[0]) == 10, "the table is indexed by SRCNN_YUVP_*");
-    if (format < 0 || format > SRCNN_YUVP_V210) return fail(SRCNN_E_ARG, "unknown packed YUV format %d", format);
-    const auto& t = T[format];
-    g.rule.kind = t.kind;
-    for (int k = 0; k < 4; ++k) g.rule.sh[k] = t.sh[k];
-    g.rule.shift = t.kind == kPk422x16 ? 16u - t.depth : 0u;
-    g.rule.mask = (1u << t.depth) - 1u;
-    g.rule.amask = t.adepth ? (1u << t.adepth) - 1u : 0u;
-    g.rule.up = (float)(1u << (t.depth - 8));
-    g.rule.down = 1.f / g.rule.up;
-    g.sx = (t.kind == kPk422x8 || t.kind == kPk422x16 || t.kind == kPkV210) ? 1 : 0;
-    g.alpha = t.adepth != 0;
-    g.align = t.align;
-    return SRCNN_OK;
-}
-
-// Everything srcnn_yuv_packed_upscale_dev refuses beyond the format itself, checked before any device lookup.
-int check_yuv_packed_args(const YuvPackedGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* src,
-                          size_t src_pitch, void* dst, size_t dst_pitch, unsigned& dw, unsigned& dh, YuvPlane& in, YuvPlane& out)
-{
-    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
-    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL frame");
-    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
-    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
-    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
-        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
-    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
-    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
-        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
-    for (int side = 0; side < 2; ++side) {
-        YuvPlane& p = side ? out : in;
-        const size_t pitch = side ? dst_pitch : src_pitch;
-        p.lo = static_cast<const unsigned char*>(side ? dst : src);
-        p.row_bytes = g.row_bytes(side ? dw : w);
-        p.rows = side ? dh : h;
-        p.pitch = pitch ? pitch : p.row_bytes;
-        if (p.pitch < p.row_bytes)
-            return fail(SRCNN_E_ARG, "%s pitch %zu is below the row of %zu bytes", side ? "output" : "input", p.pitch, p.row_bytes);
-        if ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & (g.align - 1))
-            return fail(SRCNN_E_ARG, "%s frame: base address and pitch must be multiples of %u", side ? "output" : "input", g.align);
-    }
-    if (overlaps(in, out)) return fail(SRCNN_E_ARG, "input and output frames overlap");
-    return SRCNN_OK;
-}
-
-// unpack -> chroma / alpha resample (whole planes) -> Y' band by band: Y path into a float band, then pack that band with the
-// same rows of the finished chroma and alpha planes (a packed row mixes them, and every packed format has one chroma row per
-// luma row).
-int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
-                     const YuvPlane& in, const YuvPlane& out)
-{
-    Workspace& ws = *c.ws;
-    const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
-    const unsigned band = yuv_band_rows(c, dw, dh);
-    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels):
-    // [Y U V (A) at source size] [U' V' (A') at output size] [Y' of one band]
-    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t n_y = up64((size_t)w * h), n_c = up64((size_t)cw * h), n_a = g.alpha ? n_y : 0;
-    const size_t m_c = up64((size_t)dcw * dh), m_a = g.alpha ? up64((size_t)dw * dh) : 0;
-    const size_t o_u = n_y, o_v = o_u + n_c, o_a = o_v + n_c, o_cu = o_a + n_a, o_cv = o_cu + m_c, o_ca = o_cv + m_c, o_y = o_ca + m_a;
-    int rc;
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, o_y + (size_t)dw * band))) return rc;
-    float* P = ws.planes;
-    launch_yuvp_unpack(in.lo, in.pitch, w, h, g.rule, P, P + o_u, P + o_v, g.alpha ? P + o_a : nullptr, c.s);
-    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
-    if ((rc = resample_rows_range(c, P + o_u, cw, h, dcw, dh, cfilter, 0, dh, P + o_cu))) return rc;
-    if ((rc = resample_rows_range(c, P + o_v, cw, h, dcw, dh, cfilter, 0, dh, P + o_cv))) return rc;
-    if (g.alpha && (rc = resample_rows_range(c, P + o_a, w, h, dw, dh, cfilter, 0, dh, P + o_ca))) return rc;
-    const YSource ysrc = YSource::from_plane(P);
-    unsigned char* d = const_cast<unsigned char*>(out.lo);
-    for (unsigned a = 0; a < dh; a += band) {
-        const unsigned b = std::min(dh, a + band);
-        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, P + o_y))) return rc;
-        launch_yuvp_pack(P + o_y, P + o_cu + (size_t)a * dcw, P + o_cv + (size_t)a * dcw, g.alpha ? P + o_ca + (size_t)a * dw : nullptr,
-                         dw, b - a, g.rule, d, out.pitch, a, c.s);
-    }
-    HIP_TRY(hipGetLastError());
-    return SRCNN_OK;
-}
-
-// ---- RGB(A) images (include/srcnn_amd_rgb.h) ----
-
-// srcnn_rgb_format -> RgbRule, or SRCNN_E_ARG
-int rgb_rule_from_format(const srcnn_rgb_format* f, RgbRule& g)
-{
-    if (!f) return fail(SRCNN_E_ARG, "NULL format");
-    if (f->struct_size != sizeof(srcnn_rgb_format)) return fail(SRCNN_E_ARG, "struct_size %u is not %zu", f->struct_size, sizeof(srcnn_rgb_format));
-    if (f->layout != SRCNN_RGB_INTERLEAVED && f->layout != SRCNN_RGB_PLANAR) return fail(SRCNN_E_ARG, "unknown RGB layout %d", f->layout);
-    if (f->order != SRCNN_RGB_ORDER_RGB && f->order != SRCNN_RGB_ORDER_BGR) return fail(SRCNN_E_ARG, "unknown channel order %d", f->order);
-    if (f->alpha != 0 && f->alpha != 1) return fail(SRCNN_E_ARG, "bad alpha %d", f->alpha);
-    if (f->depth != 8 && f->depth != 10 && f->depth != 12 && f->depth != 14 && f->depth != 16) return fail(SRCNN_E_ARG, "unsupported depth %d", f->depth);
-    g.planar = f->layout == SRCNN_RGB_PLANAR;
-    g.bgr = f->order == SRCNN_RGB_ORDER_BGR;
-    g.ch = 3 + f->alpha;
-    g.bps = f->depth == 8 ? 1 : 2;
-    g.mask = (1u << f->depth) - 1u;
-    g.up = (float)(1u << (f->depth - 8));
-    g.down = 1.f / g.up;
-    return SRCNN_OK;
-}
-
-// Everything srcnn_rgb_upscale_dev refuses beyond the format itself, checked before any device lookup.  conv.lo stays NULL
-// when the caller asks for no truncated Y' plane.
-int check_rgb_args(const RgbRule& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[4],
-                   const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4], void* dst_conv,
-                   size_t dst_conv_pitch, unsigned& dw, unsigned& dh, YuvPlane in[4], YuvPlane out[4], YuvPlane& conv)
-{
-    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
-    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    const int np = g.planar ? g.ch : 1;
-    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
-    for (int k = 0; k < np; ++k)
-        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
-    if (!(multiply > 0.f) || !((float)w * multiply > 0.f) || !((float)h * multiply > 0.f)) return fail(SRCNN_E_SCALE, "multiply %g", multiply);
-    // (the float products are truncated to unsigned below: keep them where that is defined, and inside the Y path's limits)
-    if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
-        return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
-    if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
-    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
-        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
-    auto describe = [&](YuvPlane& p, const void* base, size_t pitch, size_t row_bytes, unsigned rows, const char* what, int k) -> int {
-        p.lo = static_cast<const unsigned char*>(base);
-        p.row_bytes = row_bytes;
-        p.rows = rows;
-        p.pitch = pitch ? pitch : row_bytes;
-        if (p.pitch < p.row_bytes) return fail(SRCNN_E_ARG, "%s pitch %zu of plane %d is below its row of %zu bytes", what, p.pitch, k, p.row_bytes);
-        if (g.bps == 2 && ((reinterpret_cast<uintptr_t>(p.lo) | p.pitch) & 1))
-            return fail(SRCNN_E_ARG, "%s plane %d: 16-bit samples need an even base address and pitch", what, k);
-        return SRCNN_OK;
-    };
-    const size_t spp = g.planar ? 1 : (size_t)g.ch;                 // samples per pixel of one plane
-    int rc;
-    for (int k = 0; k < np; ++k) {
-        if ((rc = describe(in[k], src[k], src_pitch ? src_pitch[k] : 0, (size_t)g.bps * spp * w, h, "input", k))) return rc;
-        if ((rc = describe(out[k], dst[k], dst_pitch ? dst_pitch[k] : 0, (size_t)g.bps * spp * dw, dh, "output", k))) return rc;
-    }
-    int nout = np;
-    if (dst_conv) {
-        if ((rc = describe(conv, dst_conv, dst_conv_pitch, (size_t)g.bps * dw, dh, "dst_conv", 0))) return rc;
-        out[nout++] = conv;                                         // (np <= 4: the caller's array has room for five)
-    }
-    for (int a = 0; a < np; ++a)
-        for (int b = 0; b < nout; ++b)
-            if (overlaps(in[a], out[b])) return fail(SRCNN_E_ARG, "input plane %d overlaps output plane %d", a, b);
-    for (int a = 0; a < nout; ++a)
-        for (int b = a + 1; b < nout; ++b)
-            if (overlaps(out[a], out[b])) return fail(SRCNN_E_ARG, "output planes %d and %d overlap", a, b);
-    return SRCNN_OK;
-}
-
-// The reference's own format (8-bit interleaved R,G,B[,A], tight rows, an up-scale in both axes) goes through the fused shell
-// of srcnn_process_u8: Y' from the interleaved source (k_rs2d), then the merge with on-the-fly chroma -- no float plane of
-// source or destination size.  Everything else: unpack -> per band { Y path, chroma / alpha resample, pack }.  conv.lo == NULL:
-// no truncated Y' plane.
-int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
-              const YuvPlane out[4], const YuvPlane& conv)
-{
-    Workspace& ws = *c.ws;
-    const int cfilter = filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR;   // as J.cfilter
-    const unsigned band = yuv_band_rows(c, dw, dh);
-    int rc;
-    const bool tight = in[0].pitch == in[0].row_bytes && out[0].pitch == out[0].row_bytes && (!conv.lo || conv.pitch == conv.row_bytes);
-    // (as in process_share: the switches that force the plane resamplers select the plane shell as well)
-    bool fused_shell = g.bps == 1 && !g.planar && !g.bgr && tight && !settings().shell_unfused && !settings().resample_2pass && dw > w && dh > h;
-    TableRef cv, ch_, yv, yh;
-    if (fused_shell) {
-        if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
-        if ((rc = get_table(c, cfilter, dw, w, ch_))) return rc;
-        if ((rc = get_table(c, filter, dh, h, yv))) return rc;
-        if ((rc = get_table(c, filter, dw, w, yh))) return rc;
-        fused_shell = rs2d_fits(1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, yv->view(), yh->view()) &&
-                      rs2d_fits(g.ch - 1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, cv->view(), ch_->view());
-    }
-    if (fused_shell) {
-        if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)dw * band))) return rc;
-        float* yp = ws.planes;
-        const YSource ysrc = YSource::from_rgb(in[0].lo, g.ch);
-        unsigned char* d_out = const_cast<unsigned char*>(out[0].lo);
-        unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
-        for (unsigned a = 0; a < dh; a += band) {
-            const unsigned b = std::min(dh, a + band);
-            if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, yp))) return rc;
-            const size_t p0 = (size_t)a * dw;
-            if (!launch_merge_fused(in[0].lo, (int)w, (int)h, g.ch, yp, d_out + p0 * g.ch, d_conv ? d_conv + p0 : nullptr, (int)dw,
-                                    (int)dh, (int)a, (int)(b - a), cv->view(), ch_->view(), c.s))
-                return fail(SRCNN_E_UNSUPPORTED, "fused colour shell refused a shape it was selected for");
-        }
-        HIP_TRY(hipGetLastError());
-        return SRCNN_OK;
-    }
-    // float planes in ws.planes, each start rounded up to 64 floats (16-byte accesses in the conversion kernels):
-    // [Y Cb Cr (A) at source size] [Y' Cb' Cr' (A') of one band]
-    auto up64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t sn = up64((size_t)w * h), bn = up64((size_t)dw * band);
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)g.ch * (sn + bn)))) return rc;
-    float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* dp[4] = {nullptr, nullptr, nullptr, nullptr};
-    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
-    for (int k = 0; k < g.ch; ++k) {
-        sp[k] = ws.planes + (size_t)k * sn;
-        dp[k] = ws.planes + (size_t)g.ch * sn + (size_t)k * bn;
-    }
-    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
-        src[k] = in[k].lo; spitch[k] = in[k].pitch;
-        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
-    }
-    launch_rgb_unpack(g, src, spitch, w, h, sp, c.s);
-    const YSource ysrc = YSource::from_plane(sp[0]);
-    for (unsigned a = 0; a < dh; a += band) {
-        const unsigned b = std::min(dh, a + band);
-        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, dp[0]))) return rc;
-        for (int k = 1; k < g.ch; ++k)
-            if ((rc = resample_rows_range(c, sp[k], w, h, dw, dh, cfilter, a, b, dp[k]))) return rc;
-        launch_rgb_pack(g, dp, dw, b - a, dst, dpitch, a, const_cast<unsigned char*>(conv.lo), conv.pitch, c.s);
-    }
-    HIP_TRY(hipGetLastError());
-    return SRCNN_OK;
 }
 
 }  // namespace
@@ -2148,130 +1723,6 @@ int srcnn_debug_counts(int* tables, int* lanes)
     if (tables) *tables = nt;
     if (lanes) *lanes = nl;
     return SRCNN_OK;
-}
-
-// ---- 8-bit YUV 4:2:0 frames (include/srcnn_amd_yuv.h) ----
-int srcnn_yuv_abi_version(void) { return SRCNN_AMD_YUV_VERSION; }
-
-int srcnn_yuv420_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter,
-                             const unsigned char* const src[3], const size_t src_pitch[3],
-                             unsigned char* const dst[3], const size_t dst_pitch[3], void* stream)
-{
-    if (format != SRCNN_YUV_I420 && format != SRCNN_YUV_NV12) return fail(SRCNN_E_ARG, "unknown YUV format %d", format);
-    YuvGeom g;                              // 8-bit 4:2:0
-    g.semi = format == SRCNN_YUV_NV12;
-    unsigned dw = 0, dh = 0;
-    YuvPlane in[3], out[3];
-    int rc;
-    if ((rc = check_yuv_args(g, w, h, multiply, filter, reinterpret_cast<const void* const*>(src), src_pitch,
-                             reinterpret_cast<void* const*>(dst), dst_pitch, dw, dh, in, out))) return rc;
-    StreamCall sc(stream);
-    if (sc.rc) return sc.rc;
-    TraceRange tr("srcnn yuv420 %ux%u -> %ux%u", w, h, dw, dh);
-    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
-}
-
-// ---- YUV frames of any supported depth / chroma format (include/srcnn_amd_yuv_ex.h) ----
-int srcnn_yuv_ex_abi_version(void) { return SRCNN_AMD_YUV_EX_VERSION; }
-
-int srcnn_yuv_plane_size(const srcnn_yuv_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
-                         size_t* row_bytes)
-{
-    YuvGeom g;
-    int rc;
-    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
-    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    if (plane < 0 || plane > 2) return fail(SRCNN_E_ARG, "plane %d", plane);
-    unsigned pc = w, pr = h;
-    size_t rb = (size_t)g.bps * w;
-    if (plane > 0) {
-        pc = g.ccols(w), pr = g.crows(h);
-        rb = (size_t)g.bps * pc * (g.semi ? 2 : 1);
-        if (g.semi && plane == 2) pc = pr = 0, rb = 0;
-    }
-    if (cols) *cols = pc;
-    if (rows) *rows = pr;
-    if (row_bytes) *row_bytes = rb;
-    return SRCNN_OK;
-}
-
-int srcnn_yuv_upscale_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, float multiply, int filter,
-                          const void* const src[3], const size_t src_pitch[3],
-                          void* const dst[3], const size_t dst_pitch[3], void* stream)
-{
-    YuvGeom g;
-    unsigned dw = 0, dh = 0;
-    YuvPlane in[3], out[3];
-    int rc;
-    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
-    if ((rc = check_yuv_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
-    StreamCall sc(stream);
-    if (sc.rc) return sc.rc;
-    TraceRange tr("srcnn yuv %ux%u -> %ux%u", w, h, dw, dh);
-    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
-}
-
-// ---- packed YUV frames (include/srcnn_amd_yuv_packed.h) ----
-int srcnn_yuv_packed_abi_version(void) { return SRCNN_AMD_YUV_PACKED_VERSION; }
-
-int srcnn_yuv_packed_row_bytes(int format, unsigned w, size_t* row_bytes, unsigned* alignment)
-{
-    YuvPackedGeom g;
-    int rc;
-    if ((rc = yuv_packed_geom(format, g))) return rc;
-    if (w == 0) return fail(SRCNN_E_ARG, "zero width");
-    if (row_bytes) *row_bytes = g.row_bytes(w);
-    if (alignment) *alignment = g.align;
-    return SRCNN_OK;
-}
-
-int srcnn_yuv_packed_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter, const void* src, size_t src_pitch,
-                                 void* dst, size_t dst_pitch, void* stream)
-{
-    YuvPackedGeom g;
-    unsigned dw = 0, dh = 0;
-    YuvPlane in, out;
-    int rc;
-    if ((rc = yuv_packed_geom(format, g))) return rc;
-    if ((rc = check_yuv_packed_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
-    StreamCall sc(stream);
-    if (sc.rc) return sc.rc;
-    TraceRange tr("srcnn yuv packed %ux%u -> %ux%u", w, h, dw, dh);
-    return yuv_packed_frame(sc.c, g, w, h, dw, dh, filter, in, out);
-}
-
-// ---- RGB(A) images in device memory (include/srcnn_amd_rgb.h) ----
-int srcnn_rgb_abi_version(void) { return SRCNN_AMD_RGB_VERSION; }
-
-int srcnn_rgb_plane_size(const srcnn_rgb_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
-                         size_t* row_bytes)
-{
-    RgbRule g;
-    int rc;
-    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
-    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
-    if (plane < 0 || plane > 3) return fail(SRCNN_E_ARG, "plane %d", plane);
-    const bool used = g.planar ? plane < g.ch : plane == 0;
-    if (cols) *cols = used ? w : 0;
-    if (rows) *rows = used ? h : 0;
-    if (row_bytes) *row_bytes = used ? (size_t)g.bps * w * (g.planar ? 1 : g.ch) : 0;
-    return SRCNN_OK;
-}
-
-int srcnn_rgb_upscale_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned h, float multiply, int filter,
-                          const void* const src[4], const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4],
-                          void* dst_conv, size_t dst_conv_pitch, void* stream)
-{
-    RgbRule g;
-    unsigned dw = 0, dh = 0;
-    YuvPlane in[4], out[5], conv;
-    int rc;
-    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
-    if ((rc = check_rgb_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, dw, dh, in, out, conv))) return rc;
-    StreamCall sc(stream);
-    if (sc.rc) return sc.rc;
-    TraceRange tr("srcnn rgb %ux%u -> %ux%u", w, h, dw, dh);
-    return rgb_frame(sc.c, g, w, h, dw, dh, filter, in, out, conv);
 }
 
 }  // extern "C"

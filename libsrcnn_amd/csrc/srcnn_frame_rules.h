@@ -1,0 +1,65 @@
+// srcnn_frame_rules.h -- what a frame format comes down to for the conversion kernels: plain structs that the host fills in
+// (srcnn_frame_args.hpp) and the launchers take (srcnn_yuv.h, srcnn_rgb.h).  No HIP: the host-only sanitizer harness includes it.
+#pragma once
+#include <stddef.h>
+
+namespace srcnn {
+
+// ---- planar / semi-planar YUV, 16-bit words of 10 / 12 / 14 / 16 significant bits (include/srcnn_amd_yuv_ex.h) ----
+// How a sample of `depth` bits sits in its little-endian 16-bit word, and the exact luma scalings (s = depth - 8).
+struct Yuv16Rule {
+    unsigned rshift = 0;    // read: (word >> rshift) & mask
+    unsigned mask = 0;      // maxv = 2^depth - 1
+    unsigned lshift = 0;    // write: value << lshift
+    float down = 1.f;       // 2^-s: Y sample -> the Y path's 8-bit scale
+    float up = 1.f;         // 2^s:  Yf -> Y'
+};
+
+// ---- packed frames: one plane that interleaves Y, U, V (and A) (include/srcnn_amd_yuv_packed.h) ----
+// The memory layouts the ten public formats come down to.  One lane of the kernels owns one 16-byte chunk of a packed row.
+enum YuvPackedKind {
+    kPk422x8 = 0,    // YUY2 / UYVY / YVYU: a dword per pixel pair, byte positions in sh[]          chunk: 8 Y, 4 U, 4 V
+    kPk422x16,       // Y210 / Y212 / Y216: words Y0 U Y1 V, the value in the high bits             chunk: 4 Y, 2 U, 2 V
+    kPk444x8,        // VUYA: a dword per pixel, byte positions in sh[]                             chunk: 4 Y, U, V, A
+    kPk410,          // Y410: a dword per pixel, U | Y << 10 | V << 20 | A << 30                    chunk: 4 Y, U, V, A
+    kPk444x16,       // Y416: words U Y V A                                                         chunk: 2 Y, U, V, A
+    kPkV210,         // v210: 6 pixels in 4 dwords of three 10-bit fields                           chunk: 6 Y, 3 U, 3 V
+};
+struct YuvPackedRule {
+    int kind = kPk422x8;
+    unsigned sh[4] = {0, 0, 0, 0};   // 8-bit kinds: bit position inside the dword of Y0, U, Y1, V (4:2:2) or Y, U, V, A (4:4:4)
+    unsigned shift = 0;              // kPk422x16: 16 - depth, read word >> shift, write value << shift
+    unsigned mask = 255;             // maxv = 2^depth - 1 of Y, U, V
+    unsigned amask = 0;              // maxv of alpha; 0: the format has none
+    float down = 1.f, up = 1.f;      // 2^-s, 2^s (s = depth - 8): Y sample <-> the Y path's 8-bit scale
+};
+// tight bytes of a w-pixel packed row (srcnn_yuv_packed_row_bytes): always whole dwords
+inline size_t yuv_packed_row_bytes(int kind, unsigned w)
+{
+    switch (kind) {
+    case kPk422x8: return (size_t)4 * ((w + 1) / 2);
+    case kPk422x16: return (size_t)8 * ((w + 1) / 2);
+    case kPk444x8:
+    case kPk410: return (size_t)4 * w;
+    case kPk444x16: return (size_t)8 * w;
+    default: return (size_t)128 * ((w + 47) / 48);
+    }
+}
+// chroma samples of a w-pixel packed row: ceil(w / 2) for the 4:2:2 kinds, else w
+inline unsigned yuv_packed_chroma_cols(int kind, unsigned w)
+{
+    return kind == kPk422x8 || kind == kPk422x16 || kind == kPkV210 ? (w + 1) / 2 : w;
+}
+
+// ---- RGB(A) images (include/srcnn_amd_rgb.h): what a srcnn_rgb_format comes down to (s = depth - 8) ----
+struct RgbRule {
+    bool planar = false;    // one plane per channel instead of one plane of interleaved pixels
+    bool bgr = false;       // the first and the third channel change places
+    int ch = 3;             // channels: 3, or 4 with alpha last
+    unsigned bps = 1;       // bytes per sample: 1 (depth 8) or 2
+    unsigned mask = 0xffu;  // maxv = 2^depth - 1
+    float down = 1.f;       // 2^-s: sample -> the 8-bit scale the colour arithmetic works on
+    float up = 1.f;         // 2^s:  clamped result -> sample
+};
+
+}  // namespace srcnn

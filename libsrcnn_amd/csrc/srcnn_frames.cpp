@@ -1,0 +1,321 @@
+// srcnn_frames.cpp -- the frame calls around the Y path: integer frames in device memory in, integer frames out.
+//   include/srcnn_amd_yuv.h          srcnn_yuv420_upscale_dev        8-bit 4:2:0 (I420 / NV12)
+//   include/srcnn_amd_yuv_ex.h       srcnn_yuv_upscale_dev           planar / semi-planar, 8-16 bits, 4:2:0 / 4:2:2 / 4:4:4
+//   include/srcnn_amd_yuv_packed.h   srcnn_yuv_packed_upscale_dev    YUY2, UYVY, Y210, Y410, v210 ...
+//   include/srcnn_amd_rgb.h          srcnn_rgb_upscale_dev           RGB(A), interleaved or planar, 8-16 bits
+//
+// Every call has the same skeleton: refuse what the arguments rule out before any device lookup (srcnn_frame_args.hpp), lay
+// the float planes out in ws.planes (PlaneArena), unpack the source (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip,
+// srcnn_rgb.hip), resample chroma and alpha with chroma_filter(), and produce Y' band by band (for_each_y_band): the Y path
+// of srcnn_capi.cpp into a float band, then the call's own pack of that band.  The state shared with the other translation
+// units is srcnn_host.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "srcnn_frame_args.hpp"
+#include "srcnn_host.hpp"
+#include "srcnn_rgb.h"
+#include "srcnn_yuv.h"
+
+namespace srcnn {
+
+namespace {
+
+// Float planes in ws.planes, in the order they are taken; each start is rounded up to 64 floats (16-byte accesses in the
+// conversion kernels).
+struct PlaneArena {
+    size_t n = 0;           // floats needed so far
+    size_t take(size_t k) { const size_t o = (n + 63) & ~(size_t)63; n = o + k; return o; }
+};
+
+// chroma and alpha planes: nearest stays nearest, everything else is bilinear (as J.cfilter of srcnn_process_u8)
+int chroma_filter(int filter) { return filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR; }
+
+// Rows of Y' one pass of the Y path produces: the whole frame when its layer-2 planes fit the workspace cap (y_path_range's
+// test), else budget_band_rows.
+unsigned yuv_band_rows(const Call& c, unsigned dw, unsigned dh)
+{
+    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
+    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)dh + 4) <= G.ws_budget.load()) return dh;
+    return std::min(dh, budget_band_rows(dw));
+}
+
+// Y' in bands of `band` rows: the Y path writes rows [a, b) to yband, then after(a, b) packs them into the destination.
+template <class After>
+int for_each_y_band(Call& c, const YSource& ysrc, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned band,
+                    float* yband, After after)
+{
+    for (unsigned a = 0; a < dh; a += band) {
+        const unsigned b = std::min(dh, a + band);
+        int rc;
+        if ((rc = y_path_rows(c, ysrc, w, h, dw, dh, filter, a, b, yband))) return rc;
+        if ((rc = after(a, b))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
+// unpack -> chroma resample + pack (whole planes) -> Y' band by band.
+int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
+              const YuvPlane out[3])
+{
+    Workspace& ws = *c.ws;
+    const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    PlaneArena A;
+    const size_t o_y = A.take((size_t)w * h), o_u = A.take((size_t)cw * ch), o_v = A.take((size_t)cw * ch);
+    const size_t o_cu = A.take((size_t)dcw * dch), o_cv = A.take((size_t)dcw * dch), o_band = A.take((size_t)dw * band);
+    int rc;
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
+    float* P = ws.planes;
+    const Yuv16Rule* rule = g.bps == 2 ? &g.rule : nullptr;
+    auto unpack = [&](const YuvPlane& p, unsigned pw, unsigned ph, bool luma, float* d0, float* d1) {
+        launch_plane_unpack(p.lo, p.pitch, pw, ph, d1 != nullptr, rule, luma, d0, d1, c.s);
+    };
+    auto pack = [&](const float* s0, const float* s1, unsigned pw, unsigned ph, bool sat, const YuvPlane& p, unsigned row0) {
+        launch_plane_pack(s0, s1, pw, ph, sat, rule, const_cast<unsigned char*>(p.lo), p.pitch, row0, c.s);
+    };
+    unpack(in[0], w, h, true, P + o_y, nullptr);
+    if (g.semi) unpack(in[1], cw, ch, false, P + o_u, P + o_v);
+    else {
+        unpack(in[1], cw, ch, false, P + o_u, nullptr);
+        unpack(in[2], cw, ch, false, P + o_v, nullptr);
+    }
+    const int cfilter = chroma_filter(filter);
+    if ((rc = resample_rows_range(c, P + o_u, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cu))) return rc;
+    if ((rc = resample_rows_range(c, P + o_v, cw, ch, dcw, dch, cfilter, 0, dch, P + o_cv))) return rc;
+    if (g.semi) pack(P + o_cu, P + o_cv, dcw, dch, true, out[1], 0);
+    else {
+        pack(P + o_cu, nullptr, dcw, dch, true, out[1], 0);
+        pack(P + o_cv, nullptr, dcw, dch, true, out[2], 0);
+    }
+    return for_each_y_band(c, YSource::from_plane(P + o_y), w, h, dw, dh, filter, band, P + o_band, [&](unsigned a, unsigned b) {
+        pack(P + o_band, nullptr, dw, b - a, false, out[0], a);
+        return SRCNN_OK;
+    });
+}
+
+// unpack -> chroma / alpha resample (whole planes) -> Y' band by band, each band packed with the same rows of the finished
+// chroma and alpha planes (a packed row mixes them, and every packed format has one chroma row per luma row).
+int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                     const YuvPlane& in, const YuvPlane& out)
+{
+    Workspace& ws = *c.ws;
+    const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    // [Y U V (A) at source size] [U' V' (A') at output size] [Y' of one band]
+    PlaneArena A;
+    const size_t o_y = A.take((size_t)w * h), o_u = A.take((size_t)cw * h), o_v = A.take((size_t)cw * h);
+    const size_t o_a = A.take(g.alpha ? (size_t)w * h : 0);
+    const size_t o_cu = A.take((size_t)dcw * dh), o_cv = A.take((size_t)dcw * dh), o_ca = A.take(g.alpha ? (size_t)dw * dh : 0);
+    const size_t o_band = A.take((size_t)dw * band);
+    int rc;
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
+    float* P = ws.planes;
+    launch_yuvp_unpack(in.lo, in.pitch, w, h, g.rule, P + o_y, P + o_u, P + o_v, g.alpha ? P + o_a : nullptr, c.s);
+    const int cfilter = chroma_filter(filter);
+    if ((rc = resample_rows_range(c, P + o_u, cw, h, dcw, dh, cfilter, 0, dh, P + o_cu))) return rc;
+    if ((rc = resample_rows_range(c, P + o_v, cw, h, dcw, dh, cfilter, 0, dh, P + o_cv))) return rc;
+    if (g.alpha && (rc = resample_rows_range(c, P + o_a, w, h, dw, dh, cfilter, 0, dh, P + o_ca))) return rc;
+    unsigned char* d = const_cast<unsigned char*>(out.lo);
+    return for_each_y_band(c, YSource::from_plane(P + o_y), w, h, dw, dh, filter, band, P + o_band, [&](unsigned a, unsigned b) {
+        launch_yuvp_pack(P + o_band, P + o_cu + (size_t)a * dcw, P + o_cv + (size_t)a * dcw, g.alpha ? P + o_ca + (size_t)a * dw : nullptr,
+                         dw, b - a, g.rule, d, out.pitch, a, c.s);
+        return SRCNN_OK;
+    });
+}
+
+// The reference's own format (8-bit interleaved R,G,B[,A], tight rows, an up-scale in both axes) goes through the fused shell
+// of srcnn_process_u8: Y' from the interleaved source (k_rs2d), then the merge with on-the-fly chroma -- no float plane of
+// source or destination size.  Everything else: unpack -> per band { Y path, chroma / alpha resample, pack }.  conv.lo == NULL:
+// no truncated Y' plane.
+int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
+              const YuvPlane out[4], const YuvPlane& conv)
+{
+    Workspace& ws = *c.ws;
+    const int cfilter = chroma_filter(filter);
+    const unsigned band = yuv_band_rows(c, dw, dh);
+    int rc;
+    const bool tight = in[0].pitch == in[0].row_bytes && out[0].pitch == out[0].row_bytes && (!conv.lo || conv.pitch == conv.row_bytes);
+    // (as in process_share: the switches that force the plane resamplers select the plane shell as well)
+    bool fused_shell = g.bps == 1 && !g.planar && !g.bgr && tight && !settings().shell_unfused && !settings().resample_2pass && dw > w && dh > h;
+    TableRef cv, ch_, yv, yh;
+    if (fused_shell) {
+        if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
+        if ((rc = get_table(c, cfilter, dw, w, ch_))) return rc;
+        if ((rc = get_table(c, filter, dh, h, yv))) return rc;
+        if ((rc = get_table(c, filter, dw, w, yh))) return rc;
+        fused_shell = rs2d_fits(1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, yv->view(), yh->view()) &&
+                      rs2d_fits(g.ch - 1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, cv->view(), ch_->view());
+    }
+    if (fused_shell) {
+        if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)dw * band))) return rc;
+        float* yp = ws.planes;
+        unsigned char* d_out = const_cast<unsigned char*>(out[0].lo);
+        unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
+        return for_each_y_band(c, YSource::from_rgb(in[0].lo, g.ch), w, h, dw, dh, filter, band, yp, [&](unsigned a, unsigned b) {
+            const size_t p0 = (size_t)a * dw;
+            if (!launch_merge_fused(in[0].lo, (int)w, (int)h, g.ch, yp, d_out + p0 * g.ch, d_conv ? d_conv + p0 : nullptr, (int)dw,
+                                    (int)dh, (int)a, (int)(b - a), cv->view(), ch_->view(), c.s))
+                return fail(SRCNN_E_UNSUPPORTED, "fused colour shell refused a shape it was selected for");
+            return SRCNN_OK;
+        });
+    }
+    // [Y Cb Cr (A) at source size] [Y' Cb' Cr' (A') of one band]
+    PlaneArena A;
+    float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* dp[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t so[4], bo[4];
+    for (int k = 0; k < g.ch; ++k) so[k] = A.take((size_t)w * h);
+    for (int k = 0; k < g.ch; ++k) bo[k] = A.take((size_t)dw * band);
+    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
+    for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes + so[k]; dp[k] = ws.planes + bo[k]; }
+    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
+    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
+        src[k] = in[k].lo; spitch[k] = in[k].pitch;
+        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
+    }
+    launch_rgb_unpack(g, src, spitch, w, h, sp, c.s);
+    return for_each_y_band(c, YSource::from_plane(sp[0]), w, h, dw, dh, filter, band, dp[0], [&](unsigned a, unsigned b) {
+        for (int k = 1; k < g.ch; ++k)
+            if (int rk = resample_rows_range(c, sp[k], w, h, dw, dh, cfilter, a, b, dp[k])) return rk;
+        launch_rgb_pack(g, dp, dw, b - a, dst, dpitch, a, const_cast<unsigned char*>(conv.lo), conv.pitch, c.s);
+        return SRCNN_OK;
+    });
+}
+
+}  // namespace
+}  // namespace srcnn
+
+using namespace srcnn;
+
+extern "C" {
+
+// ---- 8-bit YUV 4:2:0 frames (include/srcnn_amd_yuv.h) ----
+int srcnn_yuv_abi_version(void) { return SRCNN_AMD_YUV_VERSION; }
+
+int srcnn_yuv420_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter,
+                             const unsigned char* const src[3], const size_t src_pitch[3],
+                             unsigned char* const dst[3], const size_t dst_pitch[3], void* stream)
+{
+    if (format != SRCNN_YUV_I420 && format != SRCNN_YUV_NV12) return fail(SRCNN_E_ARG, "unknown YUV format %d", format);
+    YuvGeom g;                              // 8-bit 4:2:0
+    g.semi = format == SRCNN_YUV_NV12;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[3], out[3];
+    int rc;
+    if ((rc = check_yuv_args(g, w, h, multiply, filter, reinterpret_cast<const void* const*>(src), src_pitch,
+                             reinterpret_cast<void* const*>(dst), dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv420 %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- YUV frames of any supported depth / chroma format (include/srcnn_amd_yuv_ex.h) ----
+int srcnn_yuv_ex_abi_version(void) { return SRCNN_AMD_YUV_EX_VERSION; }
+
+int srcnn_yuv_plane_size(const srcnn_yuv_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
+                         size_t* row_bytes)
+{
+    YuvGeom g;
+    int rc;
+    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    if (plane < 0 || plane > 2) return fail(SRCNN_E_ARG, "plane %d", plane);
+    unsigned pc = w, pr = h;
+    size_t rb = (size_t)g.bps * w;
+    if (plane > 0) {
+        pc = g.ccols(w), pr = g.crows(h);
+        rb = (size_t)g.bps * pc * (g.semi ? 2 : 1);
+        if (g.semi && plane == 2) pc = pr = 0, rb = 0;
+    }
+    if (cols) *cols = pc;
+    if (rows) *rows = pr;
+    if (row_bytes) *row_bytes = rb;
+    return SRCNN_OK;
+}
+
+int srcnn_yuv_upscale_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                          const void* const src[3], const size_t src_pitch[3],
+                          void* const dst[3], const size_t dst_pitch[3], void* stream)
+{
+    YuvGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[3], out[3];
+    int rc;
+    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
+    if ((rc = check_yuv_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- packed YUV frames (include/srcnn_amd_yuv_packed.h) ----
+int srcnn_yuv_packed_abi_version(void) { return SRCNN_AMD_YUV_PACKED_VERSION; }
+
+int srcnn_yuv_packed_row_bytes(int format, unsigned w, size_t* row_bytes, unsigned* alignment)
+{
+    YuvPackedGeom g;
+    int rc;
+    if ((rc = yuv_packed_geom(format, g))) return rc;
+    if (w == 0) return fail(SRCNN_E_ARG, "zero width");
+    if (row_bytes) *row_bytes = g.row_bytes(w);
+    if (alignment) *alignment = g.align;
+    return SRCNN_OK;
+}
+
+int srcnn_yuv_packed_upscale_dev(int format, unsigned w, unsigned h, float multiply, int filter, const void* src, size_t src_pitch,
+                                 void* dst, size_t dst_pitch, void* stream)
+{
+    YuvPackedGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in, out;
+    int rc;
+    if ((rc = yuv_packed_geom(format, g))) return rc;
+    if ((rc = check_yuv_packed_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn yuv packed %ux%u -> %ux%u", w, h, dw, dh);
+    return yuv_packed_frame(sc.c, g, w, h, dw, dh, filter, in, out);
+}
+
+// ---- RGB(A) images in device memory (include/srcnn_amd_rgb.h) ----
+int srcnn_rgb_abi_version(void) { return SRCNN_AMD_RGB_VERSION; }
+
+int srcnn_rgb_plane_size(const srcnn_rgb_format* fmt, unsigned w, unsigned h, int plane, unsigned* cols, unsigned* rows,
+                         size_t* row_bytes)
+{
+    RgbRule g;
+    int rc;
+    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
+    if (w == 0 || h == 0) return fail(SRCNN_E_ARG, "zero dimension %ux%u", w, h);
+    if (plane < 0 || plane > 3) return fail(SRCNN_E_ARG, "plane %d", plane);
+    const bool used = g.planar ? plane < g.ch : plane == 0;
+    if (cols) *cols = used ? w : 0;
+    if (rows) *rows = used ? h : 0;
+    if (row_bytes) *row_bytes = used ? (size_t)g.bps * w * (g.planar ? 1 : g.ch) : 0;
+    return SRCNN_OK;
+}
+
+int srcnn_rgb_upscale_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                          const void* const src[4], const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4],
+                          void* dst_conv, size_t dst_conv_pitch, void* stream)
+{
+    RgbRule g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[4], out[5], conv;
+    int rc;
+    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
+    if ((rc = check_rgb_args(g, w, h, multiply, filter, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, dw, dh, in, out, conv))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    TraceRange tr("srcnn rgb %ux%u -> %ux%u", w, h, dw, dh);
+    return rgb_frame(sc.c, g, w, h, dw, dh, filter, in, out, conv);
+}
+
+}  // extern "C"

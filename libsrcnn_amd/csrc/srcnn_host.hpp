@@ -1,5 +1,6 @@
 // srcnn_host.hpp -- host-side state shared by the C-ABI translation units (srcnn_capi.cpp: contexts, plumbing,
-// the device-resident hot path; srcnn_pipeline.cpp: the host-pointer pipelines and the node-level calls).
+// the device-resident hot path; srcnn_pipeline.cpp: the host-pointer pipelines and the node-level calls; srcnn_frames.cpp: the
+// YUV / RGB frame calls).
 // Internal; the public surface is include/srcnn_amd.h.
 //
 // One process may drive several CONTEXTS.  A context is one device binding with everything that lives in that
@@ -282,6 +283,24 @@ bool host_is_page_locked(const void* p);           // hipHostMalloc / hipHostReg
 // is finished first, so the call is ordered on it like the hipMemcpyAsync it replaces.
 int copy_h2d_any(Ctx& cx, void* d_dst, const void* h_src, size_t bytes, hipStream_t after);
 int copy_d2h_any(Ctx& cx, void* h_dst, const void* d_src, size_t bytes, hipStream_t after);
+
+// An eager call on a caller-visible stream: the stream's own scratch, locked while this call enqueues.
+struct StreamCall {
+    std::vector<TableRef> tables;
+    Call c;
+    std::unique_lock<std::mutex> lk;
+    int rc = SRCNN_OK;
+    explicit StreamCall(void* stream)
+    {
+        c.cx = ctx_for_stream(stream);
+        if (!c.cx) { rc = SRCNN_E_NODEVICE; return; }
+        c.s = (hipStream_t)stream;
+        c.ws = workspace_for(*c.cx, c.s);
+        c.mode = G.mode.load();
+        c.hold = &tables;
+        lk = std::unique_lock<std::mutex>(c.ws->mu);
+    }
+};
 
 // ---- the path (srcnn_capi.cpp) ----
 int check_plane(const void* in, unsigned w, unsigned h, const void* out);

@@ -4,18 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
-namespace srcnn {
+#include "srcnn_frame_rules.h"
 
-// What a srcnn_rgb_format comes down to for the conversion kernels (s = depth - 8).
-struct RgbRule {
-    bool planar = false;    // one plane per channel instead of one plane of interleaved pixels
-    bool bgr = false;       // the first and the third channel change places
-    int ch = 3;             // channels: 3, or 4 with alpha last
-    unsigned bps = 1;       // bytes per sample: 1 (depth 8) or 2
-    unsigned mask = 0xffu;  // maxv = 2^depth - 1
-    float down = 1.f;       // 2^-s: sample -> the 8-bit scale the colour arithmetic works on
-    float up = 1.f;         // 2^s:  clamped result -> sample
-};
+namespace srcnn {
 
 // Pitched integer plane(s) -> tight float planes out[0..3] = Y, Cb, Cr, A (w floats per row; out[3] only with alpha), rows
 // [0, rows), with the split arithmetic of k_rgb_split.  Interleaved: src[0] only.  At bps == 2 bases and pitches are even.

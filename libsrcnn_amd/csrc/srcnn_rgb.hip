@@ -13,12 +13,11 @@
 // planar; consecutive dwords are merged into wider accesses by the compiler), where bases and pitches are aligned for it
 // (decided once per launch); a row's last partial chunk and misaligned planes take the scalar forms, so that no byte outside a
 // row's samples is ever touched.  Grid-stride over rows x chunks.  mask and the two scalings are kernel arguments: every depth
-// runs the same instances.  The host side is srcnn_capi.cpp (srcnn_rgb_upscale_dev).
+// runs the same instances.  The host side is srcnn_frames.cpp (rgb_frame).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
+#include "srcnn_pixel_io.h"
 #include "srcnn_rgb.h"
 
 #pragma clang fp contract(off)
@@ -41,35 +40,6 @@ struct RgbIo {
     int bgr;
     int int_vec, flt_vec, conv_vec;      // dword accesses of the integer planes / float4 accesses / dword stores of conv are aligned
 };
-
-// sample j of the 4 * D (interleaved) or 4 (planar) samples packed in consecutive dwords
-template <int BPS>
-__device__ __forceinline__ unsigned sample_of(const unsigned* wd, int j)
-{
-    if constexpr (BPS == 1) return (wd[j >> 2] >> (8 * (j & 3))) & 0xffu;
-    else return (wd[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-}
-
-template <int BPS>
-__device__ __forceinline__ void put_sample(unsigned* wd, int j, unsigned v)
-{
-    if constexpr (BPS == 1) wd[j >> 2] |= v << (8 * (j & 3));
-    else wd[j >> 1] |= v << (16 * (j & 1));
-}
-
-template <int BPS>
-__device__ __forceinline__ unsigned load_scalar(const unsigned char* q)
-{
-    if constexpr (BPS == 1) return *q;
-    else return *reinterpret_cast<const unsigned short*>(q);     // 2-byte aligned: the host refuses odd planes
-}
-
-template <int BPS>
-__device__ __forceinline__ void store_scalar(unsigned char* q, unsigned v)
-{
-    if constexpr (BPS == 1) *q = (unsigned char)v;
-    else *reinterpret_cast<unsigned short*>(q) = (unsigned short)v;
-}
 
 __device__ __forceinline__ unsigned to_code(float v, float up)
 {   // MIN(255.f, v) then MAX(0.f, .) in the reference's macro forms, the exact scaling, the truncating cast
@@ -135,10 +105,10 @@ __global__ __launch_bounds__(256) void k_rgb_unpack(const RgbIo a)
         }
         const size_t o = (size_t)r * a.w + c;
         if (n == kChunkRgb && a.flt_vec) {
-            *reinterpret_cast<float4*>(a.f[0] + o) = make_float4(yv[0], yv[1], yv[2], yv[3]);
-            *reinterpret_cast<float4*>(a.f[1] + o) = make_float4(cbv[0], cbv[1], cbv[2], cbv[3]);
-            *reinterpret_cast<float4*>(a.f[2] + o) = make_float4(crv[0], crv[1], crv[2], crv[3]);
-            if constexpr (D == 4) *reinterpret_cast<float4*>(a.f[3] + o) = make_float4(av[0], av[1], av[2], av[3]);
+            store_floats_vec<kChunkRgb>(a.f[0] + o, yv);
+            store_floats_vec<kChunkRgb>(a.f[1] + o, cbv);
+            store_floats_vec<kChunkRgb>(a.f[2] + o, crv);
+            if constexpr (D == 4) store_floats_vec<kChunkRgb>(a.f[3] + o, av);
         } else {
 #pragma unroll
             for (int px = 0; px < (int)kChunkRgb; ++px) {
@@ -163,28 +133,11 @@ __global__ __launch_bounds__(256) void k_rgb_pack(const RgbIo a)
         const unsigned n = min(kChunkRgb, a.w - c);
         const size_t o = (size_t)r * a.w + c;
         const size_t dr = (size_t)a.row0 + r;                    // destination row
-        float yv[kChunkRgb], cbv[kChunkRgb], crv[kChunkRgb], av[kChunkRgb];
-        if (n == kChunkRgb && a.flt_vec) {
-            const float4 y4 = *reinterpret_cast<const float4*>(a.f[0] + o);
-            const float4 cb4 = *reinterpret_cast<const float4*>(a.f[1] + o);
-            const float4 cr4 = *reinterpret_cast<const float4*>(a.f[2] + o);
-            float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (D == 4) a4 = *reinterpret_cast<const float4*>(a.f[3] + o);
-            yv[0] = y4.x; yv[1] = y4.y; yv[2] = y4.z; yv[3] = y4.w;
-            cbv[0] = cb4.x; cbv[1] = cb4.y; cbv[2] = cb4.z; cbv[3] = cb4.w;
-            crv[0] = cr4.x; crv[1] = cr4.y; crv[2] = cr4.z; crv[3] = cr4.w;
-            av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
-        } else {
-#pragma unroll
-            for (int px = 0; px < (int)kChunkRgb; ++px) {
-                const bool in = (unsigned)px < n;
-                yv[px] = in ? a.f[0][o + px] : 0.f;
-                cbv[px] = in ? a.f[1][o + px] : 0.f;
-                crv[px] = in ? a.f[2][o + px] : 0.f;
-                av[px] = 0.f;
-                if constexpr (D == 4) av[px] = in ? a.f[3][o + px] : 0.f;
-            }
-        }
+        float yv[kChunkRgb], cbv[kChunkRgb], crv[kChunkRgb], av[kChunkRgb] = {0.f, 0.f, 0.f, 0.f};
+        load_floats<kChunkRgb>(a.f[0] + o, yv, n, a.flt_vec);
+        load_floats<kChunkRgb>(a.f[1] + o, cbv, n, a.flt_vec);
+        load_floats<kChunkRgb>(a.f[2] + o, crv, n, a.flt_vec);
+        if constexpr (D == 4) load_floats<kChunkRgb>(a.f[3] + o, av, n, a.flt_vec);
         unsigned code[kChunkRgb][D], cv[kChunkRgb];              // [pixel][channel in memory order]
 #pragma unroll
         for (int px = 0; px < (int)kChunkRgb; ++px) {
@@ -247,13 +200,7 @@ __global__ __launch_bounds__(256) void k_rgb_pack(const RgbIo a)
     }
 }
 
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-dim3 grid_for(unsigned w, unsigned rows)
-{
-    const size_t total = (size_t)((w + kChunkRgb - 1) / kChunkRgb) * rows;
-    return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 8192)));
-}
+dim3 rgb_grid(unsigned w, unsigned rows) { return grid_for((size_t)((w + kChunkRgb - 1) / kChunkRgb) * rows, 8192); }
 
 RgbIo io_of(const RgbRule& f, unsigned char* const p[4], const size_t pitch[4], float* const fl[4], unsigned w, unsigned rows)
 {
@@ -298,7 +245,7 @@ void launch_rgb_unpack(const RgbRule& f, const unsigned char* const src[4], cons
     unsigned char* p[4];
     for (int k = 0; k < 4; ++k) p[k] = const_cast<unsigned char*>(src[k]);      // (the unpack kernel only reads them)
     const RgbIo a = io_of(f, p, pitch, out, w, rows);
-    const dim3 grid = grid_for(w, rows);
+    const dim3 grid = rgb_grid(w, rows);
     RGB_DISPATCH(k_rgb_unpack, f, grid, s, a);
 }
 
@@ -312,7 +259,7 @@ void launch_rgb_pack(const RgbRule& f, const float* const in[4], unsigned w, uns
     a.row0 = row0;
     a.conv = conv; a.conv_pitch = conv_pitch;
     a.conv_vec = conv && aligned_to(conv, 4) && conv_pitch % 4 == 0;
-    const dim3 grid = grid_for(w, rows);
+    const dim3 grid = rgb_grid(w, rows);
     RGB_DISPATCH(k_rgb_pack, f, grid, s, a);
 }
 

@@ -23,13 +23,12 @@
 // stride the packed side by 32 B instead and halve the 16-byte coalescing there.  In the pack kernel the groups that only
 // pad a row to its 128-byte block are chunks like any other, with no valid sample: they are written as zero.
 //
-// Grid-stride over rows x chunks.  The host side is srcnn_capi.cpp (srcnn_yuv_packed_upscale_dev); planar and semi-planar
-// frames are srcnn_yuv.hip and srcnn_yuv16.hip.
+// Grid-stride over rows x chunks.  The host side is srcnn_frames.cpp (yuv_packed_frame); planar and semi-planar frames are
+// srcnn_yuv_planes.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
+#include "srcnn_pixel_io.h"
 #include "srcnn_yuv.h"
 
 #pragma clang fp contract(off)
@@ -81,50 +80,6 @@ __device__ __forceinline__ void store_dword(unsigned char* p, unsigned v, int io
         ps[0] = (unsigned short)v; ps[1] = (unsigned short)(v >> 16);
     } else {
         *reinterpret_cast<unsigned*>(p) = v;
-    }
-}
-
-// N floats at p, the first n of them valid: vector accesses for a whole piece where the launch allows them
-template <unsigned N>
-__device__ __forceinline__ void store_floats(float* p, const float* v, unsigned n, int vec)
-{
-    if constexpr (N == 0) return;
-    if (vec && n == N && N % 2 == 0) {
-        if constexpr (N % 4 == 0) {
-#pragma unroll
-            for (unsigned k = 0; k < N; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
-        } else if constexpr (N % 2 == 0) {
-#pragma unroll
-            for (unsigned k = 0; k < N; k += 2) *reinterpret_cast<float2*>(p + k) = make_float2(v[k], v[k + 1]);
-        }
-    } else {
-#pragma unroll
-        for (unsigned k = 0; k < N; ++k)
-            if (k < n) p[k] = v[k];
-    }
-}
-
-template <unsigned N>
-__device__ __forceinline__ void load_floats(const float* p, float* v, unsigned n, int vec)
-{
-    if constexpr (N == 0) return;
-    if (vec && n == N && N % 2 == 0) {
-        if constexpr (N % 4 == 0) {
-#pragma unroll
-            for (unsigned k = 0; k < N; k += 4) {
-                const float4 x = *reinterpret_cast<const float4*>(p + k);
-                v[k] = x.x; v[k + 1] = x.y; v[k + 2] = x.z; v[k + 3] = x.w;
-            }
-        } else if constexpr (N % 2 == 0) {
-#pragma unroll
-            for (unsigned k = 0; k < N; k += 2) {
-                const float2 x = *reinterpret_cast<const float2*>(p + k);
-                v[k] = x.x; v[k + 1] = x.y;
-            }
-        }
-    } else {
-#pragma unroll
-        for (unsigned k = 0; k < N; ++k) v[k] = k < n ? p[k] : 0.f;
     }
 }
 
@@ -293,8 +248,6 @@ __global__ __launch_bounds__(256) void k_yuvp_pack(const float* __restrict__ sy,
     }
 }
 
-inline bool aligned_to(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 int io_of(const void* base, size_t pitch)
 {
     const uintptr_t bits = reinterpret_cast<uintptr_t>(base) | (uintptr_t)pitch;
@@ -314,34 +267,18 @@ bool float_vec_ok(int kind, unsigned w)
     }
 }
 
-dim3 grid_for(size_t total) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, 4096))); }
-
-// tight bytes of a w-pixel row (srcnn_yuv_packed_row_bytes): always whole dwords
-size_t row_bytes_of(int kind, unsigned w)
-{
-    switch (kind) {
-    case kPk422x8: return (size_t)4 * ((w + 1) / 2);
-    case kPk422x16: return (size_t)8 * ((w + 1) / 2);
-    case kPk444x8:
-    case kPk410: return (size_t)4 * w;
-    case kPk444x16: return (size_t)8 * w;
-    default: return (size_t)128 * ((w + 47) / 48);
-    }
-}
-
 }  // namespace
 
 void launch_yuvp_unpack(const unsigned char* src, size_t pitch, unsigned w, unsigned rows, const YuvPackedRule& f, float* dy,
                         float* du, float* dv, float* da, hipStream_t s)
 {
-    const bool sub = f.kind == kPk422x8 || f.kind == kPk422x16 || f.kind == kPkV210;
-    const unsigned cw = sub ? (w + 1) / 2 : w;
-    const size_t rb = row_bytes_of(f.kind, w);
+    const unsigned cw = yuv_packed_chroma_cols(f.kind, w);
+    const size_t rb = yuv_packed_row_bytes(f.kind, w);
     const unsigned row_dwords = (unsigned)(rb / 4);
     const unsigned cpr = f.kind == kPkV210 ? (w + 5) / 6 : (unsigned)((rb + 15) / 16);   // v210: only the groups that carry a sample
     const int io = io_of(src, pitch);
     const int fvec = float_vec_ok(f.kind, w) && aligned_to(dy, 16) && aligned_to(du, 16) && aligned_to(dv, 16) && aligned_to(da, 16);
-    const dim3 g = grid_for((size_t)cpr * rows), b(256);
+    const dim3 g = grid_for((size_t)cpr * rows, 4096), b(256);
 #define SRCNN_YUVP_UNPACK(K) hipLaunchKernelGGL(k_yuvp_unpack<K>, g, b, 0, s, src, pitch, w, cw, rows, cpr, row_dwords, dy, du, dv, da, f, io, fvec)
     switch (f.kind) {
     case kPk422x8: SRCNN_YUVP_UNPACK(kPk422x8); break;
@@ -357,14 +294,13 @@ void launch_yuvp_unpack(const unsigned char* src, size_t pitch, unsigned w, unsi
 void launch_yuvp_pack(const float* sy, const float* su, const float* sv, const float* sa, unsigned w, unsigned rows,
                       const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s)
 {
-    const bool sub = f.kind == kPk422x8 || f.kind == kPk422x16 || f.kind == kPkV210;
-    const unsigned cw = sub ? (w + 1) / 2 : w;
-    const size_t rb = row_bytes_of(f.kind, w);
+    const unsigned cw = yuv_packed_chroma_cols(f.kind, w);
+    const size_t rb = yuv_packed_row_bytes(f.kind, w);
     const unsigned row_dwords = (unsigned)(rb / 4);
     const unsigned cpr = (unsigned)((rb + 15) / 16);                 // every chunk of the tight row, v210's padding groups included
     const int io = io_of(dst, pitch);
     const int fvec = float_vec_ok(f.kind, w) && aligned_to(sy, 16) && aligned_to(su, 16) && aligned_to(sv, 16) && aligned_to(sa, 16);
-    const dim3 g = grid_for((size_t)cpr * rows), b(256);
+    const dim3 g = grid_for((size_t)cpr * rows, 4096), b(256);
 #define SRCNN_YUVP_PACK(K) hipLaunchKernelGGL(k_yuvp_pack<K>, g, b, 0, s, sy, su, sv, sa, w, cw, rows, cpr, row_dwords, dst, pitch, row0, f, io, fvec)
     switch (f.kind) {
     case kPk422x8: SRCNN_YUVP_PACK(kPk422x8); break;

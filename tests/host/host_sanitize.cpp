@@ -12,12 +12,17 @@
 //   * concurrent ProcessSRCNN calls from 4 threads (the TSan target: the drop-in keeps no per-call state);
 //   * libsrcnn_amd/csrc/srcnn_watchdog.hpp  (the deadline around every blocking RCCL call) hammered from 4 threads, some of
 //     them toggling the timeout to 0 between calls: regions are exclusive, a no-op arm() never releases somebody else's region,
-//     a region that outlives its deadline is marked (under the lock) and aborted exactly once, stale generations are ignored.
+//     a region that outlives its deadline is marked (under the lock) and aborted exactly once, stale generations are ignored;
+//   * libsrcnn_amd/csrc/srcnn_frame_args.hpp (everything the YUV / packed / RGB frame calls decide before any device lookup:
+//     plane geometry, pitches, alignment, the end-of-plane pointer arithmetic of the overlap rules) on host buffers.
 #include <atomic>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -25,6 +30,7 @@
 #include "../../include/srcnn_amd.h"
 #include "../../include/srcnn_amd_debug.h"
 #include "../../libsrcnn_amd/csrc/resample_table.hpp"
+#include "../../libsrcnn_amd/csrc/srcnn_frame_args.hpp"
 #include "../../libsrcnn_amd/csrc/srcnn_watchdog.hpp"
 
 extern "C" {
@@ -223,6 +229,239 @@ static void check_watchdog()
     CHECK(marks.load() == m0 && aborts.load() == a0, "watchdog: a stale generation must not touch the new communicator");
 }
 
+// ---- the argument half of the frame calls (srcnn_frame_args.hpp) ----
+// The product's fail() lives in srcnn_capi.cpp; this one formats as well, so the sanitizers see every message's arguments.
+namespace srcnn {
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return code;
+}
+}  // namespace srcnn
+
+using srcnn::YuvPlane;
+
+// One checker behind one signature.  np planes per side; with conv the RGB call's dst_conv rides as dst[np] / dp[np] / out[np].
+struct Family {
+    const char* name;
+    int np;
+    bool conv;
+    unsigned align;          // of base and pitch
+    bool out_out;            // output planes over each other are refused (the RGB call only)
+    std::function<int(unsigned w, unsigned h, float mul, int filter, void* const* src, const size_t* sp, void* const* dst,
+                      const size_t* dp, YuvPlane* in, YuvPlane* out)> check;
+    int nout() const { return np + (conv ? 1 : 0); }
+};
+
+static std::vector<Family> frame_families()
+{
+    std::vector<Family> v;
+    const struct { int layout, chroma, depth, msb; } yuv[] = {
+        {SRCNN_YUV_PLANAR, SRCNN_YUV_420, 8, 0}, {SRCNN_YUV_SEMIPLANAR, SRCNN_YUV_420, 8, 0}, {SRCNN_YUV_PLANAR, SRCNN_YUV_422, 10, 0},
+        {SRCNN_YUV_SEMIPLANAR, SRCNN_YUV_420, 10, 1}, {SRCNN_YUV_PLANAR, SRCNN_YUV_444, 16, 0}, {SRCNN_YUV_SEMIPLANAR, SRCNN_YUV_444, 12, 1}};
+    for (auto& f : yuv) {
+        const srcnn_yuv_format fmt = {sizeof(srcnn_yuv_format), f.layout, f.chroma, f.depth, f.msb};
+        srcnn::YuvGeom g;
+        CHECK(srcnn::yuv_geom_from_format(&fmt, g) == SRCNN_OK, "yuv format");
+        v.push_back({"yuv", g.semi ? 2 : 3, false, g.bps, false,
+                     [g](unsigned w, unsigned h, float mul, int filter, void* const* src, const size_t* sp, void* const* dst, const size_t* dp,
+                         YuvPlane* in, YuvPlane* out) {
+                         unsigned dw = 0, dh = 0;
+                         return srcnn::check_yuv_args(g, w, h, mul, filter, src, sp, dst, dp, dw, dh, in, out);
+                     }});
+    }
+    for (int format = SRCNN_YUVP_YUY2; format <= SRCNN_YUVP_V210; ++format) {
+        srcnn::YuvPackedGeom g;
+        CHECK(srcnn::yuv_packed_geom(format, g) == SRCNN_OK, "packed format %d", format);
+        v.push_back({"packed", 1, false, g.align, false,
+                     [g](unsigned w, unsigned h, float mul, int filter, void* const* src, const size_t* sp, void* const* dst, const size_t* dp,
+                         YuvPlane* in, YuvPlane* out) {
+                         unsigned dw = 0, dh = 0;
+                         return srcnn::check_yuv_packed_args(g, w, h, mul, filter, src ? src[0] : nullptr, sp ? sp[0] : 0, dst ? dst[0] : nullptr,
+                                                             dp ? dp[0] : 0, dw, dh, in[0], out[0]);
+                     }});
+    }
+    const struct { int layout, order, alpha, depth; bool conv; } rgb[] = {
+        {SRCNN_RGB_INTERLEAVED, SRCNN_RGB_ORDER_RGB, 0, 8, true}, {SRCNN_RGB_INTERLEAVED, SRCNN_RGB_ORDER_BGR, 1, 12, true},
+        {SRCNN_RGB_PLANAR, SRCNN_RGB_ORDER_RGB, 1, 10, true}, {SRCNN_RGB_PLANAR, SRCNN_RGB_ORDER_BGR, 0, 8, false}};
+    for (auto& f : rgb) {
+        const srcnn_rgb_format fmt = {sizeof(srcnn_rgb_format), f.layout, f.order, f.alpha, f.depth};
+        srcnn::RgbRule g;
+        CHECK(srcnn::rgb_rule_from_format(&fmt, g) == SRCNN_OK, "rgb format");
+        const int np = g.planar ? g.ch : 1;
+        const bool conv = f.conv;
+        v.push_back({"rgb", np, conv, g.bps, true,
+                     [g, np, conv](unsigned w, unsigned h, float mul, int filter, void* const* src, const size_t* sp, void* const* dst,
+                                   const size_t* dp, YuvPlane* in, YuvPlane* out) {
+                         unsigned dw = 0, dh = 0;
+                         YuvPlane c;
+                         return srcnn::check_rgb_args(g, w, h, mul, filter, src, sp, dst, dp, conv && dst ? dst[np] : nullptr,
+                                                      conv && dp ? dp[np] : 0, dw, dh, in, out, c);
+                     }});
+    }
+    return v;
+}
+
+// Plane sizes written out, so that this section does not rest on the checkers' own row_bytes and rows.
+static void check_frame_geometry()
+{
+    alignas(16) unsigned char buf[16];   // never read: only described
+    void* p[5] = {buf, buf, buf, buf, buf};
+    struct Want { size_t row_bytes; unsigned rows; };
+    auto same = [](const YuvPlane& got, const Want& w) { return got.row_bytes == w.row_bytes && got.rows == w.rows && got.pitch == w.row_bytes; };
+    unsigned dw, dh;
+    YuvPlane in[5], out[5], conv;
+    {   // I420 9x7 -> 18x14: Y 9 x 7, U / V 5 x 4; output Y 18 x 14, U / V 9 x 7.  (The planes overlap: E_ARG comes last, after
+        // every plane is described.)
+        srcnn::YuvGeom g;
+        CHECK(srcnn::check_yuv_args(g, 9, 7, 2.f, 2, p, nullptr, p, nullptr, dw, dh, in, out) == SRCNN_E_ARG && dw == 18 && dh == 14, "I420 size");
+        const Want wi[3] = {{9, 7}, {5, 4}, {5, 4}}, wo[3] = {{18, 14}, {9, 7}, {9, 7}};
+        for (int k = 0; k < 3; ++k) CHECK(same(in[k], wi[k]) && same(out[k], wo[k]), "I420 plane %d", k);
+    }
+    {   // P010 (semi-planar 4:2:0, 16-bit words) 49x2 -> 98x4: Y 98 B x 2, UV 25 pairs = 100 B x 1; output 196 B x 4, 196 B x 2
+        const srcnn_yuv_format fmt = {sizeof(srcnn_yuv_format), SRCNN_YUV_SEMIPLANAR, SRCNN_YUV_420, 10, 1};
+        srcnn::YuvGeom g;
+        CHECK(srcnn::yuv_geom_from_format(&fmt, g) == SRCNN_OK, "P010");
+        CHECK(srcnn::check_yuv_args(g, 49, 2, 2.f, 2, p, nullptr, p, nullptr, dw, dh, in, out) == SRCNN_E_ARG, "P010 call");
+        const Want wi[2] = {{98, 2}, {100, 1}}, wo[2] = {{196, 4}, {196, 2}};
+        for (int k = 0; k < 2; ++k) CHECK(same(in[k], wi[k]) && same(out[k], wo[k]), "P010 plane %d", k);
+    }
+    {   // packed rows of 49 -> 98 pixels: YUY2 4 B per pair, Y210 8 B per pair, Y410 4 B, Y416 8 B per pixel, v210 128 B per 48
+        const struct { int format; size_t in_row, out_row; } T[] = {{SRCNN_YUVP_YUY2, 100, 196}, {SRCNN_YUVP_Y210, 200, 392},
+                                                                    {SRCNN_YUVP_Y410, 196, 392}, {SRCNN_YUVP_Y416, 392, 784},
+                                                                    {SRCNN_YUVP_V210, 256, 384}};
+        for (auto& t : T) {
+            srcnn::YuvPackedGeom g;
+            CHECK(srcnn::yuv_packed_geom(t.format, g) == SRCNN_OK, "packed %d", t.format);
+            CHECK(srcnn::check_yuv_packed_args(g, 49, 2, 2.f, 2, buf, 0, buf, 0, dw, dh, in[0], out[0]) == SRCNN_E_ARG, "packed %d call", t.format);
+            CHECK(same(in[0], Want{t.in_row, 2}) && same(out[0], Want{t.out_row, 4}), "packed %d: rows of %zu and %zu bytes", t.format,
+                  in[0].row_bytes, out[0].row_bytes);
+        }
+    }
+    {   // RGBA 12-bit interleaved 9x7 -> 18x14: 4 words per pixel = 72 B x 7 and 144 B x 14, dst_conv one word = 36 B x 14;
+        // planar: 18 B x 7 and 36 B x 14 per plane
+        srcnn_rgb_format fmt = {sizeof(srcnn_rgb_format), SRCNN_RGB_INTERLEAVED, SRCNN_RGB_ORDER_RGB, 1, 12};
+        srcnn::RgbRule g;
+        CHECK(srcnn::rgb_rule_from_format(&fmt, g) == SRCNN_OK, "rgb");
+        CHECK(srcnn::check_rgb_args(g, 9, 7, 2.f, 2, p, nullptr, p, nullptr, buf, 0, dw, dh, in, out, conv) == SRCNN_E_ARG, "rgb call");
+        CHECK(same(in[0], Want{72, 7}) && same(out[0], Want{144, 14}) && same(conv, Want{36, 14}), "rgba interleaved");
+        fmt.layout = SRCNN_RGB_PLANAR;
+        CHECK(srcnn::rgb_rule_from_format(&fmt, g) == SRCNN_OK, "rgb planar");
+        CHECK(srcnn::check_rgb_args(g, 9, 7, 2.f, 2, p, nullptr, p, nullptr, nullptr, 0, dw, dh, in, out, conv) == SRCNN_E_ARG, "rgb planar call");
+        for (int k = 0; k < 4; ++k) CHECK(same(in[k], Want{18, 7}) && same(out[k], Want{36, 14}), "rgba planar plane %d", k);
+    }
+}
+
+static void check_frame_args()
+{
+    constexpr int E_ARG = SRCNN_E_ARG, E_SCALE = SRCNN_E_SCALE, E_UNS = SRCNN_E_UNSUPPORTED;
+    constexpr size_t kGap = 16384;       // between plane starts of the roomy layout: far above any plane used here
+    for (const Family& F : frame_families()) {
+        const int np = F.np, nout = F.nout();
+        // one allocation, so that a plane can be moved onto or beside another one: inputs from 8 gaps in, outputs from 16 gaps in
+        std::vector<unsigned char> room(24 * kGap);
+        void *src[5] = {}, *dst[5] = {};
+        for (int k = 0; k < 5; ++k) { src[k] = room.data() + (8 + k) * kGap; dst[k] = room.data() + (16 + k) * kGap; }
+        const size_t tight[5] = {0, 0, 0, 0, 0};
+
+        // valid frames, tight and padded: every plane in an allocation of exactly its own size, both ends touched
+        const unsigned sizes[][2] = {{1, 1}, {9, 7}, {49, 2}};
+        for (auto& s : sizes)
+            for (size_t pad : {(size_t)0, (size_t)64}) {
+                YuvPlane in[5], out[5];
+                CHECK(F.check(s[0], s[1], 2.f, 2, src, tight, dst, tight, in, out) == SRCNN_OK, "%s %ux%u roomy", F.name, s[0], s[1]);
+                std::vector<std::vector<unsigned char>> mem;
+                void *xs[5] = {}, *xd[5] = {};
+                size_t sp[5] = {}, dp[5] = {};
+                for (int k = 0; k < np; ++k) {
+                    sp[k] = pad ? in[k].row_bytes + pad : 0;
+                    mem.emplace_back((in[k].row_bytes + pad) * (in[k].rows - 1) + in[k].row_bytes);
+                    xs[k] = mem.back().data();
+                }
+                for (int k = 0; k < nout; ++k) {
+                    dp[k] = pad ? out[k].row_bytes + pad : 0;
+                    mem.emplace_back((out[k].row_bytes + pad) * (out[k].rows - 1) + out[k].row_bytes);
+                    xd[k] = mem.back().data();
+                }
+                YuvPlane xin[5], xout[5];
+                CHECK(F.check(s[0], s[1], 2.f, 2, xs, sp, xd, dp, xin, xout) == SRCNN_OK, "%s %ux%u pad %zu", F.name, s[0], s[1], pad);
+                unsigned touched = 0;
+                for (int k = 0; k < np + nout; ++k) {
+                    const YuvPlane& p = k < np ? xin[k] : xout[k - np];
+                    CHECK(p.lo == mem[k].data() && p.hi() == mem[k].data() + mem[k].size(), "%s %ux%u pad %zu: plane %d ends %td bytes off",
+                          F.name, s[0], s[1], pad, k, p.hi() - (mem[k].data() + mem[k].size()));
+                    touched += p.lo[0] + p.hi()[-1];
+                }
+                CHECK(touched == 0, "fresh planes are zero");
+            }
+
+        // refusals, on a 9x7 frame with explicit tight pitches in the roomy layout
+        YuvPlane in[5], out[5], t_in[5], t_out[5];
+        CHECK(F.check(9, 7, 2.f, 2, src, tight, dst, tight, in, out) == SRCNN_OK, "%s base", F.name);
+        size_t sp[5] = {}, dp[5] = {}, osize[5] = {};
+        for (int k = 0; k < np; ++k) sp[k] = in[k].row_bytes;
+        for (int k = 0; k < nout; ++k) { dp[k] = out[k].row_bytes; osize[k] = (size_t)(out[k].hi() - out[k].lo); }
+        auto call = [&](void* const* s_, const size_t* sp_, void* const* d_, const size_t* dp_, unsigned w = 9, unsigned h = 7, float mul = 2.f,
+                        int filter = 2) { return F.check(w, h, mul, filter, s_, sp_, d_, dp_, t_in, t_out); };
+        CHECK(call(src, sp, dst, dp) == SRCNN_OK, "%s explicit pitches", F.name);
+        for (int side = 0; side < 2; ++side)
+            for (int k = 0; k < (side ? nout : np); ++k) {
+                void* p2[5]; size_t q2[5];
+                memcpy(p2, side ? dst : src, sizeof p2); memcpy(q2, side ? dp : sp, sizeof q2);
+                q2[k] -= F.align;                                        // short pitch
+                CHECK((side ? call(src, sp, dst, q2) : call(src, q2, dst, dp)) == E_ARG, "%s short pitch side %d plane %d", F.name, side, k);
+                p2[k] = nullptr;
+                CHECK((side ? call(src, sp, p2, dp) : call(p2, sp, dst, dp)) == (side && k == np ? SRCNN_OK : E_ARG),   // dst_conv is optional
+                      "%s NULL side %d plane %d", F.name, side, k);
+                if (F.align == 1) continue;
+                memcpy(p2, side ? dst : src, sizeof p2); memcpy(q2, side ? dp : sp, sizeof q2);
+                p2[k] = static_cast<unsigned char*>(p2[k]) + 1;          // misaligned base
+                CHECK((side ? call(src, sp, p2, dp) : call(p2, sp, dst, dp)) == E_ARG, "%s odd base side %d plane %d", F.name, side, k);
+                q2[k] += F.align + 1;                                    // misaligned pitch (long enough)
+                CHECK((side ? call(src, sp, dst, q2) : call(src, q2, dst, dp)) == E_ARG, "%s odd pitch side %d plane %d", F.name, side, k);
+            }
+        // every output plane against every input plane: on its first sample, on its last, and right before / behind it
+        for (int a = 0; a < np; ++a)
+            for (int b = 0; b < nout; ++b) {
+                unsigned char* lo = const_cast<unsigned char*>(in[a].lo);
+                unsigned char* hi = const_cast<unsigned char*>(in[a].hi());
+                const struct { unsigned char* at; int want; const char* what; } moves[] = {
+                    {lo, E_ARG, "same start"}, {hi - F.align, E_ARG, "starts on the input's last sample"},
+                    {lo - osize[b] + F.align, E_ARG, "ends on the input's first sample"}, {hi, SRCNN_OK, "starts right behind the input"},
+                    {lo - osize[b], SRCNN_OK, "ends right before the input"}};
+                for (auto& m : moves) {
+                    void* d2[5];
+                    memcpy(d2, dst, sizeof d2);
+                    d2[b] = m.at;
+                    CHECK(call(src, sp, d2, dp) == m.want, "%s input %d / output %d: %s", F.name, a, b, m.what);
+                }
+            }
+        // output planes over each other: refused by the RGB call, accepted by the YUV calls
+        for (int a = 0; a < nout; ++a)
+            for (int b = a + 1; b < nout; ++b) {
+                void* d2[5];
+                memcpy(d2, dst, sizeof d2);
+                d2[b] = const_cast<unsigned char*>(out[a].hi()) - F.align;
+                CHECK(call(src, sp, d2, dp) == (F.out_out ? E_ARG : SRCNN_OK), "%s outputs %d and %d overlap", F.name, a, b);
+                d2[b] = const_cast<unsigned char*>(out[a].hi());
+                CHECK(call(src, sp, d2, dp) == SRCNN_OK, "%s outputs %d and %d adjacent", F.name, a, b);
+            }
+        // scale and size limits, with the codes and in the order tests/test_*_abi.py pin
+        const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+        for (float mul : {0.f, -1.f, 0.1f, 0.05f, nan}) CHECK(call(src, sp, dst, dp, 9, 7, mul) == E_SCALE, "%s multiply %g", F.name, mul);
+        CHECK(call(src, sp, dst, dp, 9, 7, inf) == E_UNS, "%s multiply inf", F.name);
+        CHECK(call(src, sp, dst, dp, 1u << 22, 2, 4.f) == E_UNS && call(src, sp, dst, dp, 2, 1u << 20, 2.f) == E_UNS &&
+              call(src, sp, dst, dp, 60000, 60000, 2.f) == E_UNS, "%s size limits", F.name);
+        CHECK(call(src, sp, dst, dp, 0, 7) == E_ARG && call(src, sp, dst, dp, 9, 0) == E_ARG && call(src, sp, dst, dp, 9, 7, 2.f, 5) == E_ARG &&
+              call(src, sp, dst, dp, 9, 7, 2.f, -1) == E_ARG, "%s zero size / filter", F.name);
+        CHECK(call(nullptr, sp, dst, dp, 9, 7, 0.f) == E_ARG && call(src, sp, nullptr, dp, 0, 0, nan, 9) == E_ARG, "%s NULL arrays", F.name);
+    }
+}
+
 int main()
 {
     check_tables();
@@ -230,6 +469,8 @@ int main()
     check_dropin();
     check_threads();
     check_watchdog();
+    check_frame_geometry();
+    check_frame_args();
     if (g_fail) { fprintf(stderr, "host_sanitize: %d check(s) failed\n", g_fail); return 1; }
     printf("host_sanitize: all checks passed (%d stand-in device calls)\n", g_calls.load());
     return 0;

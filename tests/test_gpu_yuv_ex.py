@@ -209,7 +209,10 @@ def layout_bases(rows, pitches, offset):
 @pytest.mark.parametrize("offset,pad", [(2, 2), (6, 14), (14, 34), (2, 64), (0, 0), (0, 16)])
 @pytest.mark.parametrize("w,h,filt,mul,chroma,depth,msb", [(9, 7, 2, 2.0, "420", 10, 1), (23, 17, 3, 1.5, "422", 12, 0),
                                                            (30, 11, 0, 2.5, "444", 16, 0), (33, 20, 4, 0.75, "420", 14, 1),
-                                                           (32, 16, 2, 2.0, "420", 10, 1), (32, 16, 1, 2.0, "444", 12, 0)])
+                                                           (32, 16, 2, 2.0, "420", 10, 1), (32, 16, 1, 2.0, "444", 12, 0),
+                                                           # output luma rows of 12 samples: float4 accesses on the float side
+                                                           # while the last 8-sample chunk of every row is partial
+                                                           (6, 5, 2, 2.0, "420", 10, 1)])
 def test_pitched_and_misaligned_vs_oracle(srcnn, oracle_lib, layout, offset, pad, w, h, filt, mul, chroma, depth, msb):
     S = srcnn
     semi = layout == "semiplanar"

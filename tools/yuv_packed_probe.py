@@ -6,7 +6,7 @@ alternating call by call, each timed with device events after a warm-up.  The ya
 
 Usage: python tools/yuv_packed_probe.py [--frames N] [--out FILE]      (profiles/yuv_packed.txt is its output)
 Kernel times of the unpack and pack kernels come from a run of their own under
-`rocprofv3 --kernel-trace --stats -- python tools/yuv_packed_probe.py --frames 3` (k_yuvp_* against k_yuv_* / k_yuv16_*).
+`rocprofv3 --kernel-trace --stats -- python tools/yuv_packed_probe.py --frames 3` (k_yuvp_* against k_plane_*).
 """
 import argparse
 import os
