@@ -33,6 +33,7 @@
     /* ---- kernel selection: every choice is bit-identical and tested (production + one fallback per kernel) ---- */               \
     X(B, conv12_queue,     "SRCNN_CONV12_QUEUE",     1,     "0/1", "layer 1+2: tiles drawn from a global counter vs dealt with a static stride") \
     X(B, conv12_dma,       "SRCNN_CONV12_DMA",       1,     "0/1", "layer 1+2: weights and Y tiles staged by LDS-DMA one tile ahead vs load, wait, `ds_write`") \
+    X(B, conv12_prune,     "SRCNN_CONV12_PRUNE",     1,     "0/1", "layer 1+2: strict layer 2 skips the 15 near-dead layer-1 channels in every 32-pixel segment where they are all zero vs always multiplies all 64") \
     X(B, conv12_spread,    "SRCNN_CONV12_SPREAD",    1,     "0/1", "layer 1+2: small launches dealt in quarter tiles over up to 4x more workgroups") \
     X(B, conv3_wdma,       "SRCNN_CONV3_WDMA",       1,     "0/1", "layer 3: packed weight image staged by LDS-DMA vs a plain loop") \
     X(B, conv3_off64,      "SRCNN_CONV3_OFF64",      0,     "0/1", "layer 3: 64-bit plane offsets (chosen automatically for planes of 4 GiB or more)") \
