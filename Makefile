@@ -9,7 +9,7 @@
 #   make oracle     -> the CPU checker (and oracle/_ref where the reference tree is present)
 #   make test       -> CPU test-suite;  make gpu-test on a gfx950 box
 #   make ubench     -> tools/ubench/bin/* (microbenchmarks; hipcc, gfx950)
-#   make asan tsan  -> the host code (table builder, drop-in control flow, frame-call argument checks, oracle) under ASan+UBSan / TSan, CPU only
+#   make asan tsan  -> the host code (table builder, drop-in control flow, frame-call argument checks, owner types, oracle) under ASan+UBSan / TSan, CPU only
 #   make STRICT_ONLY=1 -> the same artefacts under libsrcnn_amd/lib/strict/ with NO non-parity kernel compiled in (no FAST /
 #                      FAST_F16 / RELAXED template instance, no srcnn_fused_f16.hip); srcnn_set_mode refuses those modes
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -32,7 +32,7 @@ else
 SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 endif
 OBJS    := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(basename $(SRCS))))
-HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
+HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
 
 PREFIX  ?= /usr/local
 ROCM    ?= /opt/rocm
@@ -95,7 +95,7 @@ gpu-test: all oracle
 
 # CPU-only sanitizer builds of the host code (no GPU sanitizer exists on this pool): tests/host/host_sanitize.cpp
 SAN_SRCS := tests/host/host_sanitize.cpp $(CSRC)/dropin.cpp
-SAN_DEPS := $(SAN_SRCS) $(CSRC)/resample_table.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_frame_rules.h oracle/srcnn_oracle.c include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
+SAN_DEPS := $(SAN_SRCS) $(CSRC)/resample_table.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_owned.hpp oracle/srcnn_oracle.c include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
 tests/host/_build/oracle_%.o: oracle/srcnn_oracle.c oracle/oracle_weights.inc
 	@mkdir -p tests/host/_build
 	gcc -O1 -g -ffp-contract=off -std=c99 -fsanitize=$(subst asan,address$(comma)undefined,$(subst tsan,thread,$*)) -fno-omit-frame-pointer -c $< -o $@

@@ -285,6 +285,9 @@ int make_context_locked(int device)
     auto cx = std::make_unique<Ctx>();
     cx->index = (int)G.ctxs.size();
     cx->device = device;
+    cx->num_cus = prop.multiProcessorCount;
+    cx->numa_node = device_numa_node(device);      // (before the first bounced copy: the bounce slots are placed by it)
+    // Not published yet: every failure below destroys it with all it has acquired by then, bounce slots included.
     // SRCNN_TRACE: where the time of creating a context goes (the first one also pays for loading the code object)
     const auto tr0 = std::chrono::steady_clock::now();
     auto stamp = [&](const char* what) {
@@ -304,25 +307,18 @@ int make_context_locked(int device)
 #ifndef SRCNN_STRICT_ONLY
     auto fw = std::make_unique<FusedF16Weights>();
     build_fused_f16_weights(*dw, *fw);
-    HIP_TRY(hipMalloc((void**)&cx->fused_w, sizeof(FusedF16Weights)));
-    struct FreeOnError {                       // the context is not published yet: a failure below must not leak its device block
-        Ctx* cx;
-        ~FreeOnError() { if (cx) { (void)hipFree(cx->fused_w); cx->fused_w = nullptr; } }
-    } guard{cx.get()};
+    if (cx->fused_w.grow(1)) return fail(SRCNN_E_HIP, "hipMalloc of the fp16 tier's weight image failed");
     stamp("fp16 tier weights built");
-    if (int rc = copy_h2d_any(*cx, cx->fused_w, fw.get(), sizeof(FusedF16Weights), nullptr)) return rc;
+    if (int rc = copy_h2d_any(*cx, cx->fused_w.data(), fw.get(), sizeof(FusedF16Weights), nullptr)) return rc;
     stamp("fp16 tier weights uploaded");
     HIP_TRY(fused_f16_prepare());
     stamp("fp16 tier kernel attributes");
     HIP_TRY(rs2d_prepare());
     stamp("resampler kernel attributes");
-    guard.cx = nullptr;
 #else
     HIP_TRY(rs2d_prepare());
     stamp("resampler kernel attributes");
 #endif
-    cx->num_cus = prop.multiProcessorCount;
-    cx->numa_node = device_numa_node(device);
     // direct copies between the devices of a node (the node-level tiled frame moves its bands with hipMemcpyPeerAsync)
     for (auto& other : G.ctxs) {
         if (other->device == device) continue;
@@ -437,13 +433,12 @@ int get_table(Call& c, int filter, unsigned dst_len, unsigned src_len, TableRef&
         d->monotone = true;
         for (unsigned u = 1; u < dst_len; ++u)
             if (t.first[u] < t.first[u - 1] || t.first[u] + t.taps[u] < t.first[u - 1] + t.taps[u - 1]) { d->monotone = false; break; }
-        HIP_TRY(hipMalloc((void**)&d->first, sizeof(int) * dst_len));
-        HIP_TRY(hipMalloc((void**)&d->taps, sizeof(int) * dst_len));
-        HIP_TRY(hipMalloc((void**)&d->weight, sizeof(double) * t.weight.size()));
+        if (d->first.grow(dst_len) || d->taps.grow(dst_len) || d->weight.grow(t.weight.size()))
+            return fail(SRCNN_E_HIP, "hipMalloc of a contribution table (%u entries) failed", dst_len);
         // (heap vectors: through the bounce slots like every other pageable source -- a tall frame's weight table is 400 KB)
-        if (int rc = copy_h2d_any(cx, d->first, t.first.data(), sizeof(int) * dst_len, nullptr)) return rc;
-        if (int rc = copy_h2d_any(cx, d->taps, t.taps.data(), sizeof(int) * dst_len, nullptr)) return rc;
-        if (int rc = copy_h2d_any(cx, d->weight, t.weight.data(), sizeof(double) * t.weight.size(), nullptr)) return rc;
+        if (int rc = copy_h2d_any(cx, d->first.data(), t.first.data(), sizeof(int) * dst_len, nullptr)) return rc;
+        if (int rc = copy_h2d_any(cx, d->taps.data(), t.taps.data(), sizeof(int) * dst_len, nullptr)) return rc;
+        if (int rc = copy_h2d_any(cx, d->weight.data(), t.weight.data(), sizeof(double) * t.weight.size(), nullptr)) return rc;
         if (cx.tables.size() >= kMaxTables) {
             // evict the least recently used tables that only the cache still references, down to half the bound.
             // Kernels launched by calls that already returned may still be reading them, hence the drain first.
@@ -537,28 +532,26 @@ bool host_is_page_locked(const void* p)
     return yes;
 }
 
-void HostBounce::release()
-{
-    if (pin) (void)hipHostFree(pin);
-    for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    pin = nullptr; slot = 0;
-}
-
 namespace {
 int bounce_ready(Ctx& cx, HostBounce& b, size_t bytes)          // b.mu held; no copy of this context is in flight
 {
     size_t want = 1u << 20;
     while (want < bytes && want < HostBounce::kSlot) want <<= 1;
-    if (want > b.slot) {
-        if (b.pin) (void)hipHostFree(b.pin);
-        b.slot = 0;
-        if (!(b.pin = static_cast<unsigned char*>(pinned_alloc(cx, 2 * want)))) return SRCNN_E_DEVMEM;
-        b.slot = want;
-    }
-    for (hipEvent_t& e : b.ev)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (int rc = b.s.pin.grow(2 * want, cx)) return rc;
+    for (Event& e : b.s.ev)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
     return SRCNN_OK;
 }
+
+// Waits, on every way out of a bounced copy, for the slot events recorded and not waited for yet: no return leaves DMA in
+// flight on a slot that the next caller (b.mu is released on return) would overwrite.  A copy that succeeds has waited itself.
+struct SlotGuard {
+    HostBounce& b;
+    bool pending[2] = {false, false};
+    hipError_t record(int k, hipStream_t s) { const hipError_t e = hipEventRecord(b.s.ev[k].get(), s); pending[k] = e == hipSuccess; return e; }
+    hipError_t wait(int k) { const bool was = pending[k]; pending[k] = false; return was ? wait_event(b.s.ev[k].get()) : hipSuccess; }
+    ~SlotGuard() { for (int k = 0; k < 2; ++k) (void)wait(k); }
+};
 }  // namespace
 
 // The bounced copies run on the stream the caller named (NULL: the default stream) -- NOT on a stream of their own: the
@@ -575,21 +568,21 @@ int copy_h2d_any(Ctx& cx, void* d_dst, const void* h_src, size_t bytes, hipStrea
     HostBounce& b = cx.bounce;
     std::lock_guard<std::mutex> lk(b.mu);
     if (int rc = bounce_ready(cx, b, bytes)) return rc;
-    const size_t SLOT = b.slot;
+    const size_t SLOT = b.slot();
+    unsigned char* const pin = b.s.pin.data();
     const unsigned char* src = static_cast<const unsigned char*>(h_src);
     unsigned char* dst = static_cast<unsigned char*>(d_dst);
-    bool used[2] = {false, false};
+    SlotGuard slots{b};
     for (size_t off = 0, i = 0; off < bytes; off += SLOT, ++i) {
         const int k = (int)(i & 1);
         const size_t len = std::min(SLOT, bytes - off);
-        if (used[k] && wait_event(b.ev[k]) != hipSuccess) return fail(SRCNN_E_HIP, "bounced H2D copy failed");
-        parallel_memcpy(b.pin + k * SLOT, src + off, len);
-        HIP_TRY(hipMemcpyAsync(dst + off, b.pin + k * SLOT, len, hipMemcpyHostToDevice, after));
-        HIP_TRY(hipEventRecord(b.ev[k], after));
-        used[k] = true;
+        if (slots.wait(k) != hipSuccess) return fail(SRCNN_E_HIP, "bounced H2D copy failed");
+        parallel_memcpy(pin + k * SLOT, src + off, len);
+        HIP_TRY(hipMemcpyAsync(dst + off, pin + k * SLOT, len, hipMemcpyHostToDevice, after));
+        HIP_TRY(slots.record(k, after));
     }
     for (int k = 0; k < 2; ++k)                      // the slots are free again (and the data is on the device) on return
-        if (used[k] && wait_event(b.ev[k]) != hipSuccess) return fail(SRCNN_E_HIP, "bounced H2D copy failed");
+        if (slots.wait(k) != hipSuccess) return fail(SRCNN_E_HIP, "bounced H2D copy failed");
     return SRCNN_OK;
 }
 
@@ -604,36 +597,28 @@ int copy_d2h_any(Ctx& cx, void* h_dst, const void* d_src, size_t bytes, hipStrea
     HostBounce& b = cx.bounce;
     std::lock_guard<std::mutex> lk(b.mu);
     if (int rc = bounce_ready(cx, b, bytes)) return rc;
-    const size_t SLOT = b.slot;
+    const size_t SLOT = b.slot();
+    unsigned char* const pin = b.s.pin.data();
     unsigned char* dst = static_cast<unsigned char*>(h_dst);
     const unsigned char* src = static_cast<const unsigned char*>(d_src);
+    SlotGuard slots{b};
     // chunk i+1 is on the copy engine while chunk i is copied out of its slot
     const size_t nchunks = (bytes + SLOT - 1) / SLOT;
     auto queue = [&](size_t i) -> int {
         const int k = (int)(i & 1);
         const size_t off = i * SLOT, len = std::min(SLOT, bytes - off);
-        HIP_TRY(hipMemcpyAsync(b.pin + k * SLOT, src + off, len, hipMemcpyDeviceToHost, after));
-        HIP_TRY(hipEventRecord(b.ev[k], after));
+        HIP_TRY(hipMemcpyAsync(pin + k * SLOT, src + off, len, hipMemcpyDeviceToHost, after));
+        HIP_TRY(slots.record(k, after));
         return SRCNN_OK;
     };
     if (int rc = queue(0)) return rc;
     for (size_t i = 0; i < nchunks; ++i) {
         const int k = (int)(i & 1);
         const size_t off = i * SLOT, len = std::min(SLOT, bytes - off);
-        if (wait_event(b.ev[k]) != hipSuccess) return fail(SRCNN_E_HIP, "bounced D2H copy failed");
+        if (slots.wait(k) != hipSuccess) return fail(SRCNN_E_HIP, "bounced D2H copy failed");
         if (i + 1 < nchunks) { if (int rc = queue(i + 1)) return rc; }
-        parallel_memcpy(dst + off, b.pin + k * SLOT, len);
+        parallel_memcpy(dst + off, pin + k * SLOT, len);
     }
-    return SRCNN_OK;
-}
-
-int grow_pinned(Ctx& cx, unsigned char*& p, size_t& have, size_t want)
-{
-    if (want <= have) return SRCNN_OK;
-    if (p) { (void)hipDeviceSynchronize(); (void)hipHostFree(p); p = nullptr; have = 0; }
-    p = static_cast<unsigned char*>(pinned_alloc(cx, want));
-    if (!p) return SRCNN_E_DEVMEM;
-    have = want;
     return SRCNN_OK;
 }
 
@@ -704,37 +689,6 @@ void parallel_memcpy(void* dst, const void* src, size_t n)
     for (auto& t : th) t.join();
 }
 
-void ProcLane::release_buffers()
-{
-    ws.release();
-    if (pin_in) (void)hipHostFree(pin_in);
-    if (pin_out) (void)hipHostFree(pin_out);
-    pin_in = pin_out = nullptr; pin_in_n = pin_out_n = 0;
-}
-
-void ProcLane::release()
-{
-    release_buffers();
-    for (auto e : band_events) (void)hipEventDestroy(e);
-    band_events.clear();
-    if (st) (void)hipStreamDestroy(st);
-    if (copy_st) (void)hipStreamDestroy(copy_st);
-    if (in_st) (void)hipStreamDestroy(in_st);
-    st = copy_st = in_st = nullptr;
-}
-
-void NodeLane::release()
-{
-    ws.release();
-    (void)hipFree(in); (void)hipFree(band);
-    in = band = nullptr; in_n = band_n = 0;
-    for (auto e : events) (void)hipEventDestroy(e);
-    events.clear();
-    if (st) (void)hipStreamDestroy(st);
-    if (copy_st) (void)hipStreamDestroy(copy_st);
-    st = copy_st = nullptr;
-}
-
 LaneLease::LaneLease(Ctx& c) : cx(&c)
 {
     std::unique_lock<std::mutex> lk(c.lane_mu);
@@ -744,10 +698,9 @@ LaneLease::LaneLease(Ctx& c) : cx(&c)
         if (lane) break;
         if (c.lanes.size() < G.max_lanes) {
             auto l = std::make_unique<ProcLane>();
-            if (hipStreamCreateWithFlags(&l->st, hipStreamNonBlocking) != hipSuccess ||
-                hipStreamCreateWithFlags(&l->copy_st, hipStreamNonBlocking) != hipSuccess ||
-                hipStreamCreateWithFlags(&l->in_st, hipStreamNonBlocking) != hipSuccess) {
-                l->release();
+            if (hipStreamCreateWithFlags(l->st.put(), hipStreamNonBlocking) != hipSuccess ||
+                hipStreamCreateWithFlags(l->copy_st.put(), hipStreamNonBlocking) != hipSuccess ||
+                hipStreamCreateWithFlags(l->in_st.put(), hipStreamNonBlocking) != hipSuccess) {
                 rc = fail(SRCNN_E_HIP, "could not create the streams of a ProcessSRCNN lane");
                 return;
             }
@@ -765,9 +718,9 @@ LaneLease::~LaneLease()
     if (!lane) return;
     // nothing of this call may still be running on the lane when the next caller takes it
     (void)hipSetDevice(cx->device);
-    (void)hipStreamSynchronize(lane->st);
-    (void)hipStreamSynchronize(lane->copy_st);
-    (void)hipStreamSynchronize(lane->in_st);
+    (void)hipStreamSynchronize(lane->st.get());
+    (void)hipStreamSynchronize(lane->copy_st.get());
+    (void)hipStreamSynchronize(lane->in_st.get());
     { std::lock_guard<std::mutex> lk(cx->lane_mu); lane->busy = false; }
     cx->lane_cv.notify_one();
 }
@@ -776,12 +729,12 @@ namespace {
 
 // RAII bracket: records an event pair around one stage on the launch stream when profiling is on.
 struct StageTimer {
-    Ctx& cx; hipStream_t s; int stage; hipEvent_t a = nullptr, b = nullptr; bool on;
-    hipEvent_t take()
+    Ctx& cx; hipStream_t s; int stage; Event a, b; bool on;
+    Event take()
     {
-        if (!cx.event_pool.empty()) { hipEvent_t e = cx.event_pool.back(); cx.event_pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
+        Event e;
+        if (!cx.event_pool.empty()) { e = std::move(cx.event_pool.back()); cx.event_pool.pop_back(); }
+        else if (hipEventCreate(e.put()) != hipSuccess) e.reset();
         return e;
     }
     StageTimer(int stage_, const Call& c) : cx(*c.cx), s(c.s), stage(stage_), on(c.timing && G.profiling.load(std::memory_order_relaxed))
@@ -790,14 +743,14 @@ struct StageTimer {
         std::lock_guard<std::mutex> lk(cx.mu);
         a = take(); b = take();
         if (!a || !b) { on = false; return; }
-        (void)hipEventRecord(a, s);
+        (void)hipEventRecord(a.get(), s);
     }
     ~StageTimer()
     {
         if (!on) return;
-        (void)hipEventRecord(b, s);
+        (void)hipEventRecord(b.get(), s);
         std::lock_guard<std::mutex> lk(cx.mu);
-        cx.spans.push_back(StageSpan{a, b, stage});
+        cx.spans.push_back(StageSpan{std::move(a), std::move(b), stage});
     }
 };
 
@@ -805,12 +758,12 @@ void drain_spans_locked(Ctx& cx)
 {
     for (auto& sp : cx.spans) {
         float ms = 0.f;
-        if (hipEventSynchronize(sp.b) == hipSuccess && hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
+        if (hipEventSynchronize(sp.b.get()) == hipSuccess && hipEventElapsedTime(&ms, sp.a.get(), sp.b.get()) == hipSuccess) {
             cx.stage_ms[sp.stage] += ms;
             cx.stage_n[sp.stage] += 1;
         }
-        cx.event_pool.push_back(sp.a);
-        cx.event_pool.push_back(sp.b);
+        cx.event_pool.push_back(std::move(sp.a));
+        cx.event_pool.push_back(std::move(sp.b));
     }
     cx.spans.clear();
 }
@@ -893,9 +846,9 @@ int resample_src_rows(Call& c, const YSource& src, unsigned sw, unsigned sh, uns
                 tv->source_span(r0, r1, lo, hi);
                 hi = std::min(hi, sh);
                 if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for rows [%u,%u)", r0, r1);
-                if ((rc = grow_ws(ws, ws.tmp, ws.tmp_n, (size_t)dw * (hi - lo)))) return rc;
-                launch_resample_rows(d_in + (size_t)lo * sw, sw, ws.tmp, dw, hi - lo, view_of(th), s);
-                mid = ws.tmp;
+                if ((rc = ws.grow(ws.tmp, (size_t)dw * (hi - lo)))) return rc;
+                launch_resample_rows(d_in + (size_t)lo * sw, sw, ws.tmp.data(), dw, hi - lo, view_of(th), s);
+                mid = ws.tmp.data();
                 mid_row_base = (int)lo;
             } else {
                 launch_resample_rows(d_in + (size_t)r0 * sw, sw, d_dst, dw, r1 - r0, view_of(th), s);
@@ -910,9 +863,9 @@ int resample_src_rows(Call& c, const YSource& src, unsigned sw, unsigned sh, uns
         const float* mid = d_in + (size_t)r0 * sw;
         if (sh != dh) {
             if (!tv && (rc = get_table(c, filter, dh, sh, tv))) return rc;
-            if ((rc = grow_ws(ws, ws.tmp, ws.tmp_n, (size_t)sw * (r1 - r0)))) return rc;
-            launch_resample_cols(d_in, sw, 0, ws.tmp, r0, r1 - r0, view_of(tv), s);
-            mid = ws.tmp;
+            if ((rc = ws.grow(ws.tmp, (size_t)sw * (r1 - r0)))) return rc;
+            launch_resample_cols(d_in, sw, 0, ws.tmp.data(), r0, r1 - r0, view_of(tv), s);
+            mid = ws.tmp.data();
         }
         launch_resample_rows(mid, sw, d_dst, dw, r1 - r0, view_of(th), s);
     }
@@ -948,38 +901,38 @@ int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw
     const unsigned ca = r0 >= 2 ? r0 - 2 : 0, cb = std::min(dh, r1 + 2);
     const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dh, cb + 4);
     int rc;
-    if ((rc = grow_ws(ws, ws.up, ws.up_n, (size_t)dw * (ub - ua)))) return rc;
+    if ((rc = ws.grow(ws.up, (size_t)dw * (ub - ua)))) return rc;
 #ifndef SRCNN_STRICT_ONLY
     const bool fused = c.mode == SRCNN_MODE_FAST_F16;
     if (fused) {
         // non-parity tier: one kernel for all three layers, no layer-2 planes at all
         {
             StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-            if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up))) return rc;
+            if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up.data()))) return rc;
         }
         {
             StageTimer t(SRCNN_STAGE_CONV12, c);
-            launch_fused_f16(ws.up, (int)dw, (int)dh, (int)ua, (int)(ub - ua), d_out, (int)r0, (int)(r1 - r0), cx.fused_w,
+            launch_fused_f16(ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), d_out, (int)r0, (int)(r1 - r0), cx.fused_w.data(),
                              cx.num_cus, c.s);
         }
         HIP_TRY(hipGetLastError());
         return SRCNN_OK;
     }
 #endif
-    if ((rc = grow_ws(ws, ws.c2, ws.c2_n, (size_t)C2N * dw * (cb - ca)))) return rc;
+    if ((rc = ws.grow(ws.c2, (size_t)C2N * dw * (cb - ca)))) return rc;
     TraceRange tr("srcnn y_path rows [%u,%u) of %ux%u", r0, r1, dw, dh);
     {
         StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-        if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up))) return rc;
+        if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up.data()))) return rc;
     }
     const size_t plane = (size_t)dw * (cb - ca);
     {
         StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_conv12(c, ws.up, (int)dw, (int)dh, (int)ua, (int)(ub - ua), ws.c2, plane, (int)ca, (int)(cb - ca));
+        run_conv12(c, ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_conv3(ws.c2, plane, (int)dw, (int)dh, (int)ca, (int)(cb - ca), d_out, (int)r0, (int)(r1 - r0),
+        launch_conv3(ws.c2.data(), plane, (int)dw, (int)dh, (int)ca, (int)(cb - ca), d_out, (int)r0, (int)(r1 - r0),
                      c.relax(), c.s);
     }
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
@@ -1105,47 +1058,22 @@ int batch_frames(Call& c, const float* d_in, unsigned w, unsigned h, unsigned nf
 // as long as the handle, whatever happens to the stream's own workspace or to the table cache in the meantime.
 struct BatchGraph {
     Ctx* cx = nullptr;
-    hipGraphExec_t exec = nullptr;
+    int device = 0;         // of cx: srcnn_batch_graph_destroy binds it, and the handle may outlive srcnn_shutdown (and with it *cx)
     hipStream_t stream = nullptr;
     Workspace ws;
     std::vector<TableRef> tables;
+    GraphExec exec;         // (last: destroyed before the scratch and the tables its nodes point at)
 };
 
+// What must happen before a context's members free themselves (srcnn_shutdown destroys the Ctx right after, on this thread,
+// with this device still bound): the device is idle, no call is left inside one of the context's sections, and the last
+// stage timings are read.  Graphs still alive keep their own references to their tables.
 void release_context(Ctx& cx)
 {
     (void)hipSetDevice(cx.device);
     (void)hipDeviceSynchronize();
-    {
-        std::lock_guard<std::mutex> lk(cx.lane_mu);
-        for (auto& l : cx.lanes) l->release();
-        cx.lanes.clear();
-    }
-    cx.node.release();
-    std::lock_guard<std::mutex> lk(cx.mu);
-    cx.tables.clear();                        // graphs still alive keep their own references
-    for (auto& kv : cx.ws) kv.second->release();
-    cx.ws.clear();
-    for (auto& sl : cx.slots) {
-        if (sl.exec) (void)hipGraphExecDestroy(sl.exec);
-        if (sl.st) (void)hipStreamDestroy(sl.st);
-        if (sl.cst) (void)hipStreamDestroy(sl.cst);
-        for (hipEvent_t* e : {&sl.e_in, &sl.e_k, &sl.e_out}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-        (void)hipFree(sl.din); (void)hipFree(sl.dout);
-        sl.ws.release();
-        sl.tables.clear();
-        sl.graph_tables.clear();
-        sl.st = sl.cst = nullptr; sl.din = sl.dout = nullptr; sl.din_n = sl.dout_n = 0;
-        sl.exec = nullptr; sl.gw = sl.gh = 0; sl.gmode = -1; sl.uses = 0;
-    }
+    std::scoped_lock all(cx.lane_mu, cx.mu, cx.bounce.mu, cx.host_call.mu);
     drain_spans_locked(cx);
-    for (auto e : cx.event_pool) (void)hipEventDestroy(e);
-    cx.event_pool.clear();
-    (void)hipFree(cx.fused_w);
-    cx.fused_w = nullptr;
-    (void)hipFree(cx.clock_buf);
-    cx.clock_buf = nullptr;
-    { std::lock_guard<std::mutex> bl(cx.bounce.mu); cx.bounce.release(); }
-    { std::lock_guard<std::mutex> hl(cx.host_call.mu); cx.host_call.release(); }
 }
 
 }  // namespace
@@ -1238,7 +1166,7 @@ void srcnn_shutdown(void)
         dying.swap(G.ctxs);
         G.stream_ctx.clear();
     }
-    for (auto& cx : dying) release_context(*cx);
+    for (auto& cx : dying) { release_context(*cx); cx.reset(); }
     t_ctx = 0;
 }
 
@@ -1254,17 +1182,17 @@ int srcnn_trim(void)
         {
             std::lock_guard<std::mutex> lk(cx->lane_mu);
             for (auto& l : cx->lanes)
-                if (!l->busy) { (void)hipStreamSynchronize(l->st); (void)hipStreamSynchronize(l->copy_st); l->release_buffers(); }
+                if (!l->busy) { (void)hipStreamSynchronize(l->st.get()); (void)hipStreamSynchronize(l->copy_st.get()); l->trim(); }
         }
         {
             std::lock_guard<std::mutex> bl(cx->bounce.mu);
             (void)hipDeviceSynchronize();
-            cx->bounce.release();
+            cx->bounce.s = {};
         }
         {
             std::lock_guard<std::mutex> hl(cx->host_call.mu);      // (a convenience call in flight holds it: trim waits for it)
             (void)hipDeviceSynchronize();
-            cx->host_call.release();
+            cx->host_call.d = {};
         }
         std::lock_guard<std::mutex> lk(cx->mu);
         bool any = false;
@@ -1382,7 +1310,8 @@ int srcnn_stream_destroy(void* stream)
         auto it = cx->ws.find((hipStream_t)stream);
         if (it != cx->ws.end()) { ws = std::move(it->second); cx->ws.erase(it); }
     }
-    if (ws) { std::lock_guard<std::mutex> wl(ws->mu); ws->release(); }
+    if (ws) { std::lock_guard<std::mutex> wl(ws->mu); }      // (a call that still enqueues on it finishes first)
+    ws.reset();
     { std::lock_guard<std::mutex> lk(G.mu); G.stream_ctx.erase((hipStream_t)stream); }
     HIP_TRY(hipStreamDestroy((hipStream_t)stream));
     return SRCNN_OK;
@@ -1458,26 +1387,25 @@ int srcnn_batch_graph_create(const float* d_in, unsigned w, unsigned h, unsigned
     if (!cx) return SRCNN_E_NODEVICE;
     auto bg = std::make_unique<BatchGraph>();
     bg->cx = cx;
+    bg->device = cx->device;
     bg->stream = (hipStream_t)stream;
     Call c;
     c.cx = cx; c.s = bg->stream; c.ws = &bg->ws; c.mode = G.mode.load(); c.hold = &bg->tables;
-    auto drop = [&](int code) { (void)hipStreamSynchronize(bg->stream); bg->ws.release(); return code; };
+    auto drop = [&](int code) { (void)hipStreamSynchronize(bg->stream); return code; };      // (bg frees what it holds after it)
     // eager run first: builds tables and grows the private workspace, so nothing allocates inside the capture
     if ((rc = batch_frames(c, d_in, w, h, nframes, d_out))) return drop(rc);
     if (hipStreamSynchronize(bg->stream) != hipSuccess) return drop(fail(SRCNN_E_HIP, "stream sync before capture failed"));
     bg->ws.frozen = true;
     c.timing = false;                                      // event pairs cannot be timed inside a capture
-    hipGraph_t gr = nullptr;
+    Graph gr;
     hipError_t e = hipStreamBeginCapture(bg->stream, hipStreamCaptureModeThreadLocal);
     if (e == hipSuccess) rc = batch_frames(c, d_in, w, h, nframes, d_out);
-    hipError_t e2 = hipStreamEndCapture(bg->stream, &gr);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        if (gr) (void)hipGraphDestroy(gr);
+    hipError_t e2 = hipStreamEndCapture(bg->stream, gr.put());
+    if (e != hipSuccess || e2 != hipSuccess)
         return drop(fail(SRCNN_E_HIP, "stream capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2)));
-    }
-    if (rc) { if (gr) (void)hipGraphDestroy(gr); return drop(rc); }
-    e = hipGraphInstantiate(&bg->exec, gr, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(gr);
+    if (rc) return drop(rc);
+    e = hipGraphInstantiate(bg->exec.put(), gr.get(), nullptr, nullptr, 0);
+    gr.reset();
     if (e != hipSuccess) return drop(fail(SRCNN_E_HIP, "hipGraphInstantiate -> %s", hipGetErrorString(e)));
     *graph = bg.release();
     return SRCNN_OK;
@@ -1488,7 +1416,7 @@ int srcnn_batch_graph_launch(void* graph)
     if (!graph) return fail(SRCNN_E_ARG, "graph == NULL");
     BatchGraph* b = static_cast<BatchGraph*>(graph);
     if (int rc = bind(*b->cx)) return rc;
-    HIP_TRY(hipGraphLaunch(b->exec, b->stream));
+    HIP_TRY(hipGraphLaunch(b->exec.get(), b->stream));
     return SRCNN_OK;
 }
 
@@ -1496,10 +1424,8 @@ int srcnn_batch_graph_destroy(void* graph)
 {
     if (!graph) return SRCNN_OK;
     BatchGraph* b = static_cast<BatchGraph*>(graph);
-    (void)hipSetDevice(b->cx->device);
+    (void)hipSetDevice(b->device);
     (void)hipStreamSynchronize(b->stream);
-    (void)hipGraphExecDestroy(b->exec);
-    b->ws.release();
     delete b;
     return SRCNN_OK;
 }
@@ -1695,7 +1621,7 @@ int srcnn_fused_diag(const float* d_up, unsigned w, unsigned h, float* d_out, un
 #else
     Ctx* cx = ctx_for_stream(stream);
     if (!cx) return SRCNN_E_NODEVICE;
-    launch_fused_f16(d_up, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, cx->fused_w, cx->num_cus, (hipStream_t)stream, d_dbg);
+    launch_fused_f16(d_up, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, cx->fused_w.data(), cx->num_cus, (hipStream_t)stream, d_dbg);
     HIP_TRY(hipGetLastError());
     return SRCNN_OK;
 #endif

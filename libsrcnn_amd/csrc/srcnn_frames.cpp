@@ -67,8 +67,8 @@ int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, un
     const size_t o_y = A.take((size_t)w * h), o_u = A.take((size_t)cw * ch), o_v = A.take((size_t)cw * ch);
     const size_t o_cu = A.take((size_t)dcw * dch), o_cv = A.take((size_t)dcw * dch), o_band = A.take((size_t)dw * band);
     int rc;
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
-    float* P = ws.planes;
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    float* P = ws.planes.data();
     const Yuv16Rule* rule = g.bps == 2 ? &g.rule : nullptr;
     auto unpack = [&](const YuvPlane& p, unsigned pw, unsigned ph, bool luma, float* d0, float* d1) {
         launch_plane_unpack(p.lo, p.pitch, pw, ph, d1 != nullptr, rule, luma, d0, d1, c.s);
@@ -111,8 +111,8 @@ int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, un
     const size_t o_cu = A.take((size_t)dcw * dh), o_cv = A.take((size_t)dcw * dh), o_ca = A.take(g.alpha ? (size_t)dw * dh : 0);
     const size_t o_band = A.take((size_t)dw * band);
     int rc;
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
-    float* P = ws.planes;
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    float* P = ws.planes.data();
     launch_yuvp_unpack(in.lo, in.pitch, w, h, g.rule, P + o_y, P + o_u, P + o_v, g.alpha ? P + o_a : nullptr, c.s);
     const int cfilter = chroma_filter(filter);
     if ((rc = resample_rows_range(c, P + o_u, cw, h, dcw, dh, cfilter, 0, dh, P + o_cu))) return rc;
@@ -150,8 +150,8 @@ int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, un
                       rs2d_fits(g.ch - 1, (int)w, (int)h, (int)dw, (int)dh, 0, (int)dh, cv->view(), ch_->view());
     }
     if (fused_shell) {
-        if ((rc = grow_ws(ws, ws.planes, ws.planes_n, (size_t)dw * band))) return rc;
-        float* yp = ws.planes;
+        if ((rc = ws.grow(ws.planes, (size_t)dw * band))) return rc;
+        float* yp = ws.planes.data();
         unsigned char* d_out = const_cast<unsigned char*>(out[0].lo);
         unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
         return for_each_y_band(c, YSource::from_rgb(in[0].lo, g.ch), w, h, dw, dh, filter, band, yp, [&](unsigned a, unsigned b) {
@@ -169,8 +169,8 @@ int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, un
     size_t so[4], bo[4];
     for (int k = 0; k < g.ch; ++k) so[k] = A.take((size_t)w * h);
     for (int k = 0; k < g.ch; ++k) bo[k] = A.take((size_t)dw * band);
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, A.n))) return rc;
-    for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes + so[k]; dp[k] = ws.planes + bo[k]; }
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes.data() + so[k]; dp[k] = ws.planes.data() + bo[k]; }
     const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};

@@ -26,6 +26,7 @@
 #include "../../include/srcnn_amd.h"
 #include "../../include/srcnn_amd_debug.h"
 #include "srcnn_kernels.h"
+#include "srcnn_owned.hpp"
 #include "srcnn_settings.hpp"
 
 namespace srcnn {
@@ -40,21 +41,43 @@ const char* last_error();
         if (e_ != hipSuccess) return ::srcnn::fail(SRCNN_E_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+struct Ctx;
+void* pinned_alloc(Ctx& cx, size_t bytes);      // page-locked, visible to every device, on the context's NUMA node
+
+// ---- ownership: srcnn_owned.hpp bound to HIP.  Every HIP resource of the host layer is a member of one of these. ----
+struct EventTraits { static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); } };
+struct StreamTraits { static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); } };
+struct GraphTraits { static void destroy(hipGraph_t g) { (void)hipGraphDestroy(g); } };
+struct GraphExecTraits { static void destroy(hipGraphExec_t g) { (void)hipGraphExecDestroy(g); } };
+using Event = Owned<hipEvent_t, EventTraits>;
+using Stream = Owned<hipStream_t, StreamTraits>;
+using Graph = Owned<hipGraph_t, GraphTraits>;
+using GraphExec = Owned<hipGraphExec_t, GraphExecTraits>;
+
+struct DevAlloc {
+    static void drain() { (void)hipDeviceSynchronize(); }      // kernels launched earlier (any stream) may still be using the old block
+    static int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? SRCNN_OK : fail(SRCNN_E_DEVMEM, "hipMalloc(%zu bytes) failed", bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedAlloc {          // grow(want, cx): page-locked memory is placed by the context's NUMA node
+    static void drain() { (void)hipDeviceSynchronize(); }
+    static int alloc(void** p, size_t bytes, Ctx& cx) { return (*p = pinned_alloc(cx, bytes)) ? SRCNN_OK : SRCNN_E_DEVMEM; }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+struct BounceAlloc : PinnedAlloc { static void drain() {} };      // (grown under HostBounce::mu: no copy is in flight)
+template <class T> using DevBuf = GrowBuf<T, DevAlloc>;
+using PinnedBuf = GrowBuf<unsigned char, PinnedAlloc>;
+
 struct DeviceTable {          // one uploaded AxisTable; freed only when the last reference goes
-    int* first = nullptr;
-    int* taps = nullptr;
-    double* weight = nullptr;
+    DevBuf<int> first, taps;
+    DevBuf<double> weight;
     int stride = 0;
     int max_taps = 0;
     unsigned long long stamp = 0;      // LRU clock of the cache
     // host copies (tiny) so that band planners can ask "which source rows does destination range [a,b) read"
     std::vector<int> h_first, h_taps;
     bool monotone = false;             // first[] and first[]+taps[] both non-decreasing: a tile's span is given by its ends
-    DeviceTable() = default;
-    DeviceTable(const DeviceTable&) = delete;
-    DeviceTable& operator=(const DeviceTable&) = delete;
-    ~DeviceTable() { (void)hipFree(first); (void)hipFree(taps); (void)hipFree(weight); }
-    DevAxisTable view() const { return DevAxisTable{first, taps, weight, stride, max_taps, monotone ? 1 : 0, h_first.data(), h_taps.data()}; }
+    DevAxisTable view() const { return DevAxisTable{first.data(), taps.data(), weight.data(), stride, max_taps, monotone ? 1 : 0, h_first.data(), h_taps.data()}; }
     // source index range [lo, hi) read by destination indices [a, b)
     void source_span(unsigned a, unsigned b, unsigned& lo, unsigned& hi) const
     {
@@ -65,26 +88,29 @@ struct DeviceTable {          // one uploaded AxisTable; freed only when the las
 };
 using TableRef = std::shared_ptr<DeviceTable>;
 
-struct Workspace {          // scratch of one stream / graph / lane; grow-only
+struct Scratch {            // the buffers of a Workspace: movable, so that a workspace that lives on is emptied by assignment
+    DevBuf<float> tmp;      // first resampler pass
+    DevBuf<float> up;       // upscaled Y (band)
+    DevBuf<float> c2;       // 32 layer-2 planes (band)
+    DevBuf<float> planes;   // colour shell: split planes / Y' / resized chroma planes
+    DevBuf<unsigned char> bytes;
+    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size()) + bytes.size(); }
+};
+struct Workspace : Scratch {          // scratch of one stream / graph / lane; grow-only
     std::mutex mu;          // held while a call enqueues work that uses this scratch
-    float* tmp = nullptr;   size_t tmp_n = 0;    // first resampler pass
-    float* up = nullptr;    size_t up_n = 0;     // upscaled Y (band)
-    float* c2 = nullptr;    size_t c2_n = 0;     // 32 layer-2 planes (band)
-    float* planes = nullptr; size_t planes_n = 0; // colour shell: split planes / Y' / resized chroma planes
-    unsigned char* bytes = nullptr; size_t bytes_n = 0;
+    // raw, and freed here by hand: run_conv12 allocates it, and that function's text is part of the kernel fingerprint (build.py)
     unsigned* queue = nullptr;                   // two words: the tile queue of k_conv12_mfma launches on this workspace's stream
     bool queue_dirty = false;                    // a call failed after launching: zero the counters before the next launch
     bool frozen = false;    // a captured graph has these pointers baked in: growing is an error
-    size_t footprint() const { return sizeof(float) * (tmp_n + up_n + c2_n + planes_n) + bytes_n; }
-    void release()
+    template <class T>
+    int grow(DevBuf<T>& b, size_t want)          // b: one of this workspace's buffers
     {
-        (void)hipFree(tmp); (void)hipFree(up); (void)hipFree(c2); (void)hipFree(planes); (void)hipFree(bytes); (void)hipFree(queue);
-        tmp = up = c2 = planes = nullptr; bytes = nullptr; queue = nullptr;
-        tmp_n = up_n = c2_n = planes_n = bytes_n = 0;
+        if (want > b.size() && frozen) return fail(SRCNN_E_ARG, "workspace of a captured graph cannot grow (%zu > %zu elements)", want, b.size());
+        return b.grow(want);
     }
+    void clear() { static_cast<Scratch&>(*this) = {}; (void)hipFree(queue); queue = nullptr; }
+    ~Workspace() { (void)hipFree(queue); }
 };
-
-struct Ctx;
 
 // One invocation of the path: on which context and stream it runs, on which scratch, with which numerics.  The mode is
 // read ONCE at the public entry point, so a concurrent srcnn_set_mode never changes a call half way through, and
@@ -111,18 +137,19 @@ struct Call {
     }
 };
 
-struct StageSpan { hipEvent_t a, b; int stage; };
+struct StageSpan { Event a, b; int stage; };
 
 struct StreamSlot {         // one lane of the host-stream path; lives until srcnn_shutdown
-    hipStream_t st = nullptr;          // kernels (slot 0's stream carries the kernels of BOTH slots)
-    hipStream_t cst = nullptr;         // this slot's copies, in both directions
-    hipEvent_t e_in = nullptr, e_k = nullptr, e_out = nullptr;   // frame landed / kernels done / result copied out
-    float* din = nullptr;  size_t din_n = 0;
-    float* dout = nullptr; size_t dout_n = 0;
+    Stream st;                         // kernels (slot 0's stream carries the kernels of BOTH slots)
+    Stream cst;                        // this slot's copies, in both directions
+    Event e_in, e_k, e_out;            // frame landed / kernels done / result copied out
+    DevBuf<float> din, dout;
     Workspace ws;                      // private: the captured graph has its pointers baked in
     std::vector<TableRef> tables;      // references taken by eager runs (trimmed by the runs themselves)
-    std::vector<TableRef> graph_tables; // references baked into `exec`: live exactly as long as the graph
-    hipGraphExec_t exec = nullptr;     // captured kernel sequence for (gw, gh, gmode)
+    struct Frozen {                    // retired as one: graph = {} (and ws.frozen = false)
+        GraphExec exec;                // captured kernel sequence for (gw, gh, gmode)
+        std::vector<TableRef> tables;  // references baked into `exec`: live exactly as long as the graph
+    } graph;
     unsigned gw = 0, gh = 0; int gmode = -1;
     unsigned uses = 0;                 // eager runs at the current shape (capture needs one first)
     int graph_verdict = 0;             // use_graph == 1 ("auto"): 0 = not measured yet, 1 = replay is cheap, 2 = replay burns host CPU: plain launches
@@ -135,13 +162,11 @@ struct StreamSlot {         // one lane of the host-stream path; lives until src
 // context; further callers wait for one.
 struct ProcLane {
     bool busy = false;
-    hipStream_t st = nullptr, copy_st = nullptr, in_st = nullptr;   // kernels / results out (D2H) / source rows in (H2D)
+    Stream st, copy_st, in_st;                // kernels / results out (D2H) / source rows in (H2D)
     Workspace ws;
-    unsigned char* pin_in = nullptr;  size_t pin_in_n = 0;
-    unsigned char* pin_out = nullptr; size_t pin_out_n = 0;
-    std::vector<hipEvent_t> band_events;      // per band: kernels done, result landed, source rows in
-    void release_buffers();
-    void release();
+    struct Staging { PinnedBuf in, out; } pin;
+    std::vector<Event> band_events;           // per band: kernels done, result landed, source rows in
+    void trim() { ws.clear(); pin = {}; }     // an idle lane gives its memory back (the caller has waited for its streams)
 };
 constexpr size_t kDefaultMaxLanes = 4;   // per context; env SRCNN_MAX_LANES (1..64) overrides
 constexpr unsigned kClockSlots = 8192;   // layer-1+2 launches the clock probe can hold before it wraps
@@ -150,12 +175,10 @@ constexpr size_t kMaxTables = 64;      // cache bound per context; only unrefere
 // Per-context buffers of the node-level tiled frame (srcnn_y_upscale2x_f32_node_dev): the slab of the source frame this
 // context's band reads, and the band it produces before it is copied to the root device.
 struct NodeLane {
-    hipStream_t st = nullptr, copy_st = nullptr;
+    Stream st, copy_st;
     Workspace ws;
-    float* in = nullptr;   size_t in_n = 0;
-    float* band = nullptr; size_t band_n = 0;
-    std::vector<hipEvent_t> events;
-    void release();
+    DevBuf<float> in, band;
+    std::vector<Event> events;
 };
 
 // Pageable host memory never goes to a HIP copy.  Above 128 KB the runtime pins the caller's pages IN PLACE for the transfer
@@ -166,20 +189,20 @@ struct NodeLane {
 // memcpy + DMA, double-buffered, at memcpy speed -- which is what the runtime's own staging path costs too.
 struct HostBounce {
     std::mutex mu;                      // one bounced copy at a time per context
-    unsigned char* pin = nullptr;       // 2 slots of `slot` bytes, allocated on first use
-    size_t slot = 0;                    // grows with the largest copy seen, 1 MB ... kSlot: page-locking 32 MB costs 5-80 ms, and
-                                        // the first copy of a process is the 50 KB weight image of srcnn_init
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Slots {                      // srcnn_trim: s = {}
+        GrowBuf<unsigned char, BounceAlloc> pin;   // 2 slots, allocated on first use.  A slot grows with the largest copy seen,
+                                        // 1 MB ... kSlot: page-locking 32 MB costs 5-80 ms, and the first copy of a process is the
+                                        // 50 KB weight image of srcnn_init
+        Event ev[2];
+    } s;
+    size_t slot() const { return s.pin.size() / 2; }
     static constexpr size_t kSlot = 16u << 20;
-    void release();
 };
 // device buffers of the host-pointer convenience calls (srcnn_y_path_f32 and what is built on it): grow-only; a call holds
 // `mu` from its H2D to its D2H, so such calls are serialised per context (they shared the NULL stream before as well)
 struct HostCallBuffers {
     std::mutex mu;
-    float* d_in = nullptr;  size_t d_in_n = 0;
-    float* d_out = nullptr; size_t d_out_n = 0;
-    void release() { (void)hipFree(d_in); (void)hipFree(d_out); d_in = d_out = nullptr; d_in_n = d_out_n = 0; }
+    struct Bufs { DevBuf<float> in, out; } d;      // srcnn_trim: d = {}
 };
 
 struct Ctx {
@@ -188,13 +211,14 @@ struct Ctx {
     int numa_node = -1;     // host NUMA node next to the device (-1: unknown)
     std::mutex mu;          // tables, ws map, spans, event pool
     std::vector<StageSpan> spans;          // recorded, not yet read
-    std::vector<hipEvent_t> event_pool;    // recycled events
+    std::vector<Event> event_pool;         // recycled events
     double stage_ms[SRCNN_STAGE_COUNT] = {0, 0, 0};
     unsigned long long stage_n[SRCNN_STAGE_COUNT] = {0, 0, 0};
     int num_cus = 256;
+    // raw like Workspace::queue, and for the same reason (run_conv12 reads it): freed by ~Ctx
     unsigned long long* clock_buf = nullptr;   // srcnn_debug_clock_probe: kClockSlots x (cycles, ticks), one slot per conv12 launch
     std::atomic<unsigned> clock_n{0};
-    FusedF16Weights* fused_w = nullptr;   // device copy of the fused fp16 kernel's weight image
+    DevBuf<FusedF16Weights> fused_w;      // device copy of the fused fp16 kernel's weight image
     std::map<std::tuple<int, unsigned, unsigned>, TableRef> tables;
     unsigned long long table_clock = 0;
     std::map<hipStream_t, std::unique_ptr<Workspace>> ws;
@@ -207,6 +231,7 @@ struct Ctx {
     NodeLane node;
     HostBounce bounce;
     HostCallBuffers host_call;
+    ~Ctx() { (void)hipFree(clock_buf); }
 };
 
 struct Global {
@@ -246,36 +271,8 @@ int context_count();
 Ctx* context_at(int k);
 
 // ---- scratch / tables ----
-template <class T>
-int grow(T*& p, size_t& have, size_t want)
-{
-    if (want <= have) return SRCNN_OK;
-    if (p) {
-        // kernels launched earlier (any stream) may still be using the old block: drain before freeing it
-        (void)hipDeviceSynchronize();
-        (void)hipFree(p);
-        p = nullptr; have = 0;
-    }
-    void* q = nullptr;
-    if (hipMalloc(&q, want * sizeof(T)) != hipSuccess)
-        return fail(SRCNN_E_DEVMEM, "hipMalloc(%zu bytes) failed", want * sizeof(T));
-    p = static_cast<T*>(q);
-    have = want;
-    return SRCNN_OK;
-}
-
-template <class T>
-int grow_ws(Workspace& ws, T*& p, size_t& have, size_t want)
-{
-    if (want <= have) return SRCNN_OK;
-    if (ws.frozen) return fail(SRCNN_E_ARG, "workspace of a captured graph cannot grow (%zu > %zu elements)", want, have);
-    return grow(p, have, want);
-}
-
 int get_table(Call& c, int filter, unsigned dst_len, unsigned src_len, TableRef& out);
 Workspace* workspace_for(Ctx& cx, hipStream_t s);
-void* pinned_alloc(Ctx& cx, size_t bytes);      // page-locked, visible to every device, on the context's NUMA node
-int grow_pinned(Ctx& cx, unsigned char*& p, size_t& have, size_t want);
 bool pinned_by_library(const void* p, size_t n);   // [p, p+n) lies inside a block from srcnn_host_alloc_pinned
 bool host_is_page_locked(const void* p);           // hipHostMalloc / hipHostRegister memory (asks the runtime)
 // Blocking copies between device memory and ANY host memory (see HostBounce): page-locked host memory goes straight to the copy

@@ -128,20 +128,20 @@ int stream_on_ctx(Ctx& cx, const float* in, unsigned w, unsigned h, unsigned nfr
     const int nslots = nframes > 1 ? 2 : 1;
     for (int i = 0; i < nslots && !rc; ++i) {
         StreamSlot& sl = cx.slots[i];
-        if (!sl.st && hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking) != hipSuccess) rc = fail(SRCNN_E_HIP, "stream create");
-        if (!rc && !sl.cst && hipStreamCreateWithFlags(&sl.cst, hipStreamNonBlocking) != hipSuccess) rc = fail(SRCNN_E_HIP, "stream create");
-        for (hipEvent_t* e : {&sl.e_in, &sl.e_k, &sl.e_out})
-            if (!rc && !*e && hipEventCreateWithFlags(e, kBlockingEvent) != hipSuccess) rc = fail(SRCNN_E_HIP, "event create");
+        if (!sl.st && hipStreamCreateWithFlags(sl.st.put(), hipStreamNonBlocking) != hipSuccess) rc = fail(SRCNN_E_HIP, "stream create");
+        if (!rc && !sl.cst && hipStreamCreateWithFlags(sl.cst.put(), hipStreamNonBlocking) != hipSuccess) rc = fail(SRCNN_E_HIP, "stream create");
+        for (Event* e : {&sl.e_in, &sl.e_k, &sl.e_out})
+            if (!rc && !*e && hipEventCreateWithFlags(e->put(), kBlockingEvent) != hipSuccess) rc = fail(SRCNN_E_HIP, "event create");
         if (!rc && (sl.gw != w || sl.gh != h || sl.gmode != mode)) sl.graph_verdict = 0;
         if (!rc && (sl.gw != w || sl.gh != h || sl.gmode != mode)) {     // shape or mode changed: drop the graph first,
-            if (sl.exec) { (void)wait_stream(cx.slots[0].st); (void)hipGraphExecDestroy(sl.exec); sl.exec = nullptr; }
+            if (sl.graph.exec) (void)wait_stream(cx.slots[0].st.get());
+            sl.graph = {};
             sl.ws.frozen = false;                                          // then its buffers may move again
-            sl.graph_tables.clear();
             sl.tables.clear();
             sl.gw = w; sl.gh = h; sl.gmode = mode; sl.uses = 0;
         }
-        if (!rc) rc = grow(sl.din, sl.din_n, in_n);
-        if (!rc) rc = grow(sl.dout, sl.dout_n, out_n);
+        if (!rc) rc = sl.din.grow(in_n);
+        if (!rc) rc = sl.dout.grow(out_n);
     }
     if (rc) return rc;
     // Pipeline.  Copies run on the slots' copy-only streams and every copy/kernel dependency that involves a copy is
@@ -156,10 +156,10 @@ int stream_on_ctx(Ctx& cx, const float* in, unsigned w, unsigned h, unsigned nfr
     auto copy_frame = [&](unsigned f) {
         StreamSlot& sl = cx.slots[f % nslots];
         // (a buffer that could not be page-locked is never handed to the runtime as it is: HostBounce)
-        if (wait_event(sl.e_k, &capture_mu) != hipSuccess ||
-            (out_locked ? hipMemcpyAsync(out + f * out_n, sl.dout, out_b, hipMemcpyDeviceToHost, sl.cst) != hipSuccess
-                        : copy_d2h_any(cx, out + f * out_n, sl.dout, out_b, sl.cst) != SRCNN_OK) ||
-            hipEventRecord(sl.e_out, sl.cst) != hipSuccess) copy_err = 1;
+        if (wait_event(sl.e_k.get(), &capture_mu) != hipSuccess ||
+            (out_locked ? hipMemcpyAsync(out + f * out_n, sl.dout.data(), out_b, hipMemcpyDeviceToHost, sl.cst.get()) != hipSuccess
+                        : copy_d2h_any(cx, out + f * out_n, sl.dout.data(), out_b, sl.cst.get()) != SRCNN_OK) ||
+            hipEventRecord(sl.e_out.get(), sl.cst.get()) != hipSuccess) copy_err = 1;
         copied.publish(f + 1);
     };
     std::thread copier;
@@ -170,7 +170,7 @@ int stream_on_ctx(Ctx& cx, const float* in, unsigned w, unsigned h, unsigned nfr
             copy_frame(f);
         }
     });
-    hipStream_t ks = cx.slots[0].st;       // ALL kernels go to one stream: frames back to back, never two frames' kernels
+    hipStream_t ks = cx.slots[0].st.get(); // ALL kernels go to one stream: frames back to back, never two frames' kernels
                                            // sharing the chip (that costs more than it overlaps: the persistent layer-1+2
                                            // kernel partitions its tiles over the workgroups it expects to be resident)
     // use_graph: 0 = plain launches; 2 = one hipGraph per slot, replayed per frame, whatever it costs; 1 = the same, KEPT ONLY
@@ -200,57 +200,54 @@ int stream_on_ctx(Ctx& cx, const float* in, unsigned w, unsigned h, unsigned nfr
             // the slot's previous frame: its kernels are done (the copier saw e_k) once its D2H has been queued; wait for
             // that D2H to finish before din / dout are reused
             if (threaded && !copied.wait_for(f - nslots)) { rc = fail(SRCNN_E_HIP, "frame stream cancelled"); break; }
-            if (wait_event(sl.e_out) != hipSuccess) { rc = fail(SRCNN_E_HIP, "D2H"); break; }
+            if (wait_event(sl.e_out.get()) != hipSuccess) { rc = fail(SRCNN_E_HIP, "D2H"); break; }
         }
         // frame in: also resolved on the host (the previous frame's kernels keep the device busy meanwhile)
-        if ((in_locked ? hipMemcpyAsync(sl.din, in + f * in_n, in_b, hipMemcpyHostToDevice, sl.cst) != hipSuccess
-                       : copy_h2d_any(cx, sl.din, in + f * in_n, in_b, sl.cst) != SRCNN_OK) ||
-            hipEventRecord(sl.e_in, sl.cst) != hipSuccess || wait_event(sl.e_in) != hipSuccess) {
+        if ((in_locked ? hipMemcpyAsync(sl.din.data(), in + f * in_n, in_b, hipMemcpyHostToDevice, sl.cst.get()) != hipSuccess
+                       : copy_h2d_any(cx, sl.din.data(), in + f * in_n, in_b, sl.cst.get()) != SRCNN_OK) ||
+            hipEventRecord(sl.e_in.get(), sl.cst.get()) != hipSuccess || wait_event(sl.e_in.get()) != hipSuccess) {
             rc = fail(SRCNN_E_HIP, "H2D"); break;
         }
-        if (graph_now && sl.uses >= 1 && !sl.exec) {
+        if (graph_now && sl.uses >= 1 && !sl.graph.exec) {
             // The slot has run this shape eagerly once: tables and workspaces exist, so the kernel sequence
             // can be captured without any allocation inside the capture.  The graph's table references are kept apart
             // from the eager runs' (which trim theirs), for exactly as long as the graph lives.
-            hipGraph_t graph = nullptr;
+            Graph graph;
             sl.ws.frozen = true;
             c.timing = false;              // event pairs cannot be timed inside a capture
-            c.hold = &sl.graph_tables;
+            c.hold = &sl.graph.tables;
             {
                 std::lock_guard<std::mutex> cap(capture_mu);
                 if (hipStreamBeginCapture(ks, hipStreamCaptureModeThreadLocal) != hipSuccess) rc = fail(SRCNN_E_HIP, "begin capture");
-                if (!rc) rc = y_path_frame(c, sl.din, w, h, 2 * w, 2 * h, SRCNN_FILTER_BICUBIC, sl.dout);
-                if (hipStreamEndCapture(ks, &graph) != hipSuccess && !rc) rc = fail(SRCNN_E_HIP, "end capture");
+                if (!rc) rc = y_path_frame(c, sl.din.data(), w, h, 2 * w, 2 * h, SRCNN_FILTER_BICUBIC, sl.dout.data());
+                if (hipStreamEndCapture(ks, graph.put()) != hipSuccess && !rc) rc = fail(SRCNN_E_HIP, "end capture");
             }
             c.timing = true;
             c.hold = &sl.tables;
-            if (!rc && hipGraphInstantiate(&sl.exec, graph, nullptr, nullptr, 0) != hipSuccess) rc = fail(SRCNN_E_HIP, "graph instantiate");
-            if (graph) (void)hipGraphDestroy(graph);
-            if (rc) { sl.ws.frozen = false; sl.graph_tables.clear(); break; }
+            if (!rc && hipGraphInstantiate(sl.graph.exec.put(), graph.get(), nullptr, nullptr, 0) != hipSuccess) rc = fail(SRCNN_E_HIP, "graph instantiate");
+            if (rc) { sl.graph = {}; sl.ws.frozen = false; break; }
         }
-        if (graph_now && sl.exec) {
+        if (graph_now && sl.graph.exec) {
             if (probe_replays == 0) { probe_cpu0 = process_cpu_seconds(); probe_t0 = std::chrono::steady_clock::now(); }
-            if (hipGraphLaunch(sl.exec, ks) != hipSuccess) { rc = fail(SRCNN_E_HIP, "graph launch"); break; }
+            if (hipGraphLaunch(sl.graph.exec.get(), ks) != hipSuccess) { rc = fail(SRCNN_E_HIP, "graph launch"); break; }
             ++probe_replays;
             ++g_stream_graph_frames;
         } else {
             ++g_stream_plain_frames;
-            if (sl.exec) {
+            if (sl.graph.exec) {
                 // an eager call (use_graph == 0) on a slot that still holds a captured graph of this shape: retire the graph
                 // first.  Its workspace is frozen (pointers baked in), so an eager run that needs more scratch -- a larger
                 // srcnn_set_workspace_limit since the capture -- could not grow it; and nothing should keep a graph alive
                 // that the caller no longer asks for.  The next use_graph call captures again after one eager frame.
                 (void)wait_stream(ks);
-                (void)hipGraphExecDestroy(sl.exec);
-                sl.exec = nullptr;
+                sl.graph = {};
                 sl.ws.frozen = false;
-                sl.graph_tables.clear();
             }
             if (sl.tables.size() > 16) sl.tables.clear();   // eager runs re-take their references every frame
-            rc = y_path_frame(c, sl.din, w, h, 2 * w, 2 * h, SRCNN_FILTER_BICUBIC, sl.dout);
+            rc = y_path_frame(c, sl.din.data(), w, h, 2 * w, 2 * h, SRCNN_FILTER_BICUBIC, sl.dout.data());
             if (rc) break;
         }
-        if (hipEventRecord(sl.e_k, ks) != hipSuccess) { rc = fail(SRCNN_E_HIP, "event record"); break; }
+        if (hipEventRecord(sl.e_k.get(), ks) != hipSuccess) { rc = fail(SRCNN_E_HIP, "event record"); break; }
         ++sl.uses;
         if (threaded) launched.publish(f + 1);
         else copy_frame(f);
@@ -258,8 +255,8 @@ int stream_on_ctx(Ctx& cx, const float* in, unsigned w, unsigned h, unsigned nfr
     if (rc) launched.cancel();             // the copier stops at the first frame that was never launched
     if (threaded) copier.join();
     for (int i = 0; i < nslots; ++i) {
-        if (cx.slots[i].st) (void)wait_stream(cx.slots[i].st);
-        if (cx.slots[i].cst) (void)wait_stream(cx.slots[i].cst);
+        if (cx.slots[i].st) (void)wait_stream(cx.slots[i].st.get());
+        if (cx.slots[i].cst) (void)wait_stream(cx.slots[i].cst.get());
     }
     if (!rc && copy_err) rc = fail(SRCNN_E_HIP, "a device-to-host copy of the frame stream failed");
     return rc;
@@ -279,7 +276,7 @@ struct AsyncLink {
     bool done = false, valid = false;
     bool leased = false;        // the job holds its lane: lanes are taken in chain order, or later jobs could take them all and
                                 // wait for a predecessor that waits for a lane
-    hipEvent_t ev = nullptr;
+    Event ev;
     int device = 0;
     void settle(bool ok)
     {
@@ -294,7 +291,7 @@ struct AsyncLink {
         int cur = -1;                              // (the last reference may go on an application thread: leave its device as it was)
         (void)hipGetDevice(&cur);
         (void)hipSetDevice(device);
-        (void)hipEventDestroy(ev);
+        ev.reset();
         if (cur >= 0) (void)hipSetDevice(cur);
     }
 };
@@ -370,7 +367,7 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     if (lease.rc) return lease.rc;
     ProcLane& L = *lease.lane;
     Workspace& ws = L.ws;
-    hipStream_t s = L.st;
+    const hipStream_t s = L.st.get(), copy_st = L.copy_st.get(), in_st = L.in_st.get();
     std::vector<TableRef> tables;
     Call c;
     c.cx = &cx; c.s = s; c.ws = &ws; c.mode = J.mode; c.hold = &tables;
@@ -382,8 +379,8 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     // A lane that once served a much larger image gives its memory back before it grows for this one
     {
         const size_t need = n * d + (size_t)(R1 - R0) * dw * (d + 1 + 4 + 8) + (size_t)C2N * dw * std::min<size_t>(R1 - R0, budget_band_rows(dw)) * 4;
-        const size_t have = ws.footprint() + L.pin_in_n + L.pin_out_n;
-        if (have > (256u << 20) && have > 8 * need) { (void)wait_stream(L.st); (void)wait_stream(L.copy_st); L.release_buffers(); }
+        const size_t have = ws.footprint() + L.pin.in.size() + L.pin.out.size();
+        if (have > (256u << 20) && have > 8 * need) { (void)wait_stream(s); (void)wait_stream(copy_st); L.trim(); }
     }
 
     // ---- which source rows does this share read?  (the Y path's vertical taps + halo, and the chroma taps) ----
@@ -418,19 +415,19 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     // ---- device buffers (the lane's grow-only scratch) ----
     const size_t share_px = (size_t)(R1 - R0) * dw;
     //   bytes:  [source image (whole-frame geometry; only rows lo..hi are ever written/read)] [out bands] [conv bands]
-    if ((rc = grow_ws(ws, ws.bytes, ws.bytes_n, n * d + share_px * d + share_px))) return rc;
-    unsigned char* d_rgb = ws.bytes;
-    unsigned char* d_out = ws.bytes + n * d;                 // row R0 at offset 0
+    if ((rc = ws.grow(ws.bytes, n * d + share_px * d + share_px))) return rc;
+    unsigned char* d_rgb = ws.bytes.data();
+    unsigned char* d_out = d_rgb + n * d;                    // row R0 at offset 0
     unsigned char* d_conv = d_out + share_px * d;
     //   planes: [Y' of the share] and, on the plane path only, [Y Cb Cr A at source size] [Cb' Cr' A' of the share]
     const size_t planes_need = share_px + (fused_shell ? 0 : 4 * n + 3 * share_px);
-    if ((rc = grow_ws(ws, ws.planes, ws.planes_n, planes_need))) return rc;
-    float* yp = ws.planes;                                    // Y', row R0 at offset 0
+    if ((rc = ws.grow(ws.planes, planes_need))) return rc;
+    float* yp = ws.planes.data();                                  // Y', row R0 at offset 0
     float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
     float* dp[4] = {yp, nullptr, nullptr, nullptr};
     if (!fused_shell) {
-        for (int k = 0; k < 4; ++k) sp[k] = ws.planes + share_px + k * n;
-        for (int k = 1; k < 4; ++k) dp[k] = ws.planes + share_px + 4 * n + (k - 1) * share_px;
+        for (int k = 0; k < 4; ++k) sp[k] = yp + share_px + k * n;
+        for (int k = 1; k < 4; ++k) dp[k] = yp + share_px + 4 * n + (k - 1) * share_px;
     }
 
     // ---- bands ----
@@ -441,13 +438,13 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     unsigned max_band = 0;
     for (unsigned b = 0; b < nb; ++b) max_band = std::max(max_band, cuts[b + 1] - cuts[b]);
     const bool no_planes = c.mode == SRCNN_MODE_FAST_F16;           // the fused kernel has no layer-2 planes
-    if (!no_planes && (rc = grow_ws(ws, ws.c2, ws.c2_n, (size_t)C2N * dw * std::min(dh, max_band + 4)))) return rc;
-    if ((rc = grow_ws(ws, ws.up, ws.up_n, (size_t)dw * std::min(dh, max_band + 12)))) return rc;
-    if (!fused_shell && (rc = grow_ws(ws, ws.tmp, ws.tmp_n, (size_t)std::max(w, dw) * std::max(h, std::min(dh, max_band + 12))))) return rc;
+    if (!no_planes && (rc = ws.grow(ws.c2, (size_t)C2N * dw * std::min(dh, max_band + 4)))) return rc;
+    if ((rc = ws.grow(ws.up, (size_t)dw * std::min(dh, max_band + 12)))) return rc;
+    if (!fused_shell && (rc = ws.grow(ws.tmp, (size_t)std::max(w, dw) * std::max(h, std::min(dh, max_band + 12))))) return rc;
     while (L.band_events.size() < 3 * nb + 1) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, kBlockingEvent));
-        L.band_events.push_back(e);
+        Event e;
+        HIP_TRY(hipEventCreateWithFlags(e.put(), kBlockingEvent));
+        L.band_events.push_back(std::move(e));
     }
 
     const size_t out_bytes = share_px * d;
@@ -477,8 +474,8 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
             // HIP copy: HostBounce in srcnn_host.hpp; the call waits once, at its end)
             const unsigned char* from = J.rgb + off;
             if (!small_in_locked) {
-                memcpy(L.pin_in + (off - src_off), J.rgb + off, nbytes);
-                from = L.pin_in + (off - src_off);
+                memcpy(L.pin.in.data() + (off - src_off), J.rgb + off, nbytes);
+                from = L.pin.in.data() + (off - src_off);
             }
             HIP_TRY(hipMemcpyAsync(d_rgb + off, from, nbytes, hipMemcpyHostToDevice, s));
         } else {
@@ -490,12 +487,12 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
             // profiles/r03_wait_cost.txt).  SRCNN_DEVICE_WAIT_IN=1 selects it for A/B runs.
             const unsigned char* from = J.rgb + off;
             if (!in_pinned) {
-                parallel_memcpy(L.pin_in + (off - src_off), J.rgb + off, nbytes);
-                from = L.pin_in + (off - src_off);
+                parallel_memcpy(L.pin.in.data() + (off - src_off), J.rgb + off, nbytes);
+                from = L.pin.in.data() + (off - src_off);
             }
-            hipEvent_t ev = L.band_events[2 * nb + n_staged++];
-            HIP_TRY(hipMemcpyAsync(d_rgb + off, from, nbytes, hipMemcpyHostToDevice, L.in_st));
-            HIP_TRY(hipEventRecord(ev, L.in_st));
+            hipEvent_t ev = L.band_events[2 * nb + n_staged++].get();
+            HIP_TRY(hipMemcpyAsync(d_rgb + off, from, nbytes, hipMemcpyHostToDevice, in_st));
+            HIP_TRY(hipEventRecord(ev, in_st));
             if (settings().device_wait_in) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
             else if (wait_event(ev) != hipSuccess) return fail(SRCNN_E_HIP, "stage-in copy");
         }
@@ -519,12 +516,12 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     std::thread prefault;
     bool prefaulting = false;
     if (small) {
-        if (!small_in_locked && (rc = grow_pinned(cx, L.pin_in, L.pin_in_n, src_bytes))) return rc;
-        if (!small_out_locked && (rc = grow_pinned(cx, L.pin_out, L.pin_out_n, out_bytes + share_px))) return rc;
+        if (!small_in_locked && (rc = L.pin.in.grow(src_bytes, cx))) return rc;
+        if (!small_out_locked && (rc = L.pin.out.grow(out_bytes + share_px, cx))) return rc;
     }
     if (!small) {
-        if (!in_pinned && (rc = grow_pinned(cx, L.pin_in, L.pin_in_n, src_bytes))) return rc;
-        if (!out_pinned && (rc = grow_pinned(cx, L.pin_out, L.pin_out_n, out_bytes + share_px))) return rc;
+        if (!in_pinned && (rc = L.pin.in.grow(src_bytes, cx))) return rc;
+        if (!out_pinned && (rc = L.pin.out.grow(out_bytes + share_px, cx))) return rc;
         unsigned char* o0 = J.out + (size_t)R0 * dw * d;
         unsigned char* c0 = J.conv ? J.conv + (size_t)R0 * dw : nullptr;
         if (!out_pinned) {
@@ -555,8 +552,8 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
             // resolved on the HOST by default (this thread polls the predecessor's last-kernel event, then queues): a device-side
             // hipStreamWaitEvent across streams is resolved by a thread of the runtime on this ROCm and measured slower
             // (SRCNN_ASYNC_CHAIN=2 selects it for A/B runs)
-            if (settings().async_chain == 2) HIP_TRY(hipStreamWaitEvent(s, a.ev, 0));
-            else if (wait_event(a.ev) != hipSuccess) return fail(SRCNN_E_HIP, "waiting for the previous asynchronous job's kernels");
+            if (settings().async_chain == 2) HIP_TRY(hipStreamWaitEvent(s, a.ev.get(), 0));
+            else if (wait_event(a.ev.get()) != hipSuccess) return fail(SRCNN_E_HIP, "waiting for the previous asynchronous job's kernels");
         }
         return SRCNN_OK;
     };
@@ -564,8 +561,8 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
         if (!J.mine) return;
         AsyncLink& m = *J.mine;
         m.device = cx.device;
-        bool ok = m.ev || hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventRecord(m.ev, s) == hipSuccess;
+        bool ok = m.ev || hipEventCreateWithFlags(m.ev.put(), hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventRecord(m.ev.get(), s) == hipSuccess;
         m.settle(ok);
     };
 
@@ -595,14 +592,14 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
         if ((rc = stage_rows(hi))) return rc;
         if ((rc = run_band(R0, R1))) return rc;
         chain_out();
-        unsigned char* to_rgb = small_out_locked ? J.out + (size_t)R0 * dw * d : L.pin_out;
-        unsigned char* to_conv = small_out_locked ? (J.conv ? J.conv + (size_t)R0 * dw : nullptr) : L.pin_out + out_bytes;
+        unsigned char* to_rgb = small_out_locked ? J.out + (size_t)R0 * dw * d : L.pin.out.data();
+        unsigned char* to_conv = small_out_locked ? (J.conv ? J.conv + (size_t)R0 * dw : nullptr) : L.pin.out.data() + out_bytes;
         HIP_TRY(hipMemcpyAsync(to_rgb, d_out, out_bytes, hipMemcpyDeviceToHost, s));
         if (J.conv) HIP_TRY(hipMemcpyAsync(to_conv, d_conv, share_px, hipMemcpyDeviceToHost, s));
         HIP_TRY(wait_stream(s));
         if (!small_out_locked) {
-            memcpy(J.out + (size_t)R0 * dw * d, L.pin_out, out_bytes);
-            if (J.conv) memcpy(J.conv + (size_t)R0 * dw, L.pin_out + out_bytes, share_px);
+            memcpy(J.out + (size_t)R0 * dw * d, L.pin.out.data(), out_bytes);
+            if (J.conv) memcpy(J.conv + (size_t)R0 * dw, L.pin.out.data() + out_bytes, share_px);
         }
         return SRCNN_OK;
     }
@@ -612,8 +609,8 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     // sides, the output produced in bands (bit-identical to the whole frame, tests/test_gpu_parity.py::
     // test_bands_equal_whole_frame), each band's D2H on the copy stream while the next band computes, and a helper thread
     // that fans each landed band out to the caller's buffers.  The helper blocks on events; it never spins.
-    unsigned char* pin_rgb = out_pinned ? nullptr : L.pin_out;
-    unsigned char* pin_conv = out_pinned ? nullptr : L.pin_out + out_bytes;
+    unsigned char* pin_rgb = out_pinned ? nullptr : L.pin.out.data();
+    unsigned char* pin_conv = out_pinned ? nullptr : L.pin.out.data() + out_bytes;
     std::atomic<int> copy_err{0};
     // SRCNN_TRACE stamps, microseconds since entry: first band queued, last band's kernels done, last band landed in staging
     std::atomic<long> us_first_queued{0}, us_kernels_done{0}, us_landed{0};
@@ -621,20 +618,20 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
     Handoff enqueued;                       // bands whose kernels have been queued (their "computed" event recorded)
     auto d2h_band = [&](unsigned b) {
         const size_t p0 = (size_t)(cuts[b] - R0) * dw, pn = (size_t)(cuts[b + 1] - cuts[b]) * dw;
-        const hipError_t kd = wait_event(L.band_events[2 * b]);
+        const hipError_t kd = wait_event(L.band_events[2 * b].get());
         if (b + 1 == nb) us_kernels_done = since();
         const size_t g0 = (size_t)cuts[b] * dw;
         unsigned char* to_rgb = out_pinned ? J.out + g0 * d : pin_rgb + p0 * d;          // page-locked result: no staging
         unsigned char* to_conv = out_pinned ? (J.conv ? J.conv + g0 : nullptr) : pin_conv + p0;
         if (kd != hipSuccess ||
-            hipMemcpyAsync(to_rgb, d_out + p0 * d, pn * d, hipMemcpyDeviceToHost, L.copy_st) != hipSuccess ||
-            (J.conv && hipMemcpyAsync(to_conv, d_conv + p0, pn, hipMemcpyDeviceToHost, L.copy_st) != hipSuccess) ||
-            hipEventRecord(L.band_events[2 * b + 1], L.copy_st) != hipSuccess) { copy_err = 1; return false; }
+            hipMemcpyAsync(to_rgb, d_out + p0 * d, pn * d, hipMemcpyDeviceToHost, copy_st) != hipSuccess ||
+            (J.conv && hipMemcpyAsync(to_conv, d_conv + p0, pn, hipMemcpyDeviceToHost, copy_st) != hipSuccess) ||
+            hipEventRecord(L.band_events[2 * b + 1].get(), copy_st) != hipSuccess) { copy_err = 1; return false; }
         return true;
     };
     auto fan_band = [&](unsigned b) {
         TraceRange tf("srcnn fan-out band %u", b);
-        if (wait_event(L.band_events[2 * b + 1]) != hipSuccess) { copy_err = 1; return; }
+        if (wait_event(L.band_events[2 * b + 1].get()) != hipSuccess) { copy_err = 1; return; }
         if (b + 1 == nb) us_landed = since();
         if (out_pinned) return;                                 // the band landed in the caller's buffer itself
         const size_t p0 = (size_t)(cuts[b] - R0) * dw, pn = (size_t)(cuts[b + 1] - cuts[b]) * dw;
@@ -673,7 +670,7 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
         if (!launch_rc) launch_rc = stage_rows(b + 1 == nb ? hi : upto);
         if (!launch_rc) launch_rc = chain_in();
         if (!launch_rc) launch_rc = run_band(cuts[b], cuts[b + 1]);
-        if (!launch_rc && hipEventRecord(L.band_events[2 * b], s) != hipSuccess) launch_rc = fail(SRCNN_E_HIP, "band %u event record failed", b);
+        if (!launch_rc && hipEventRecord(L.band_events[2 * b].get(), s) != hipSuccess) launch_rc = fail(SRCNN_E_HIP, "band %u event record failed", b);
         if (!launch_rc && b + 1 == nb) chain_out();
         if (launch_rc) { enqueued.cancel(); break; }
         if (b == 0) us_first_queued = since();
@@ -686,7 +683,7 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
         for (unsigned b = 0; b < nb; ++b) fan_band(b);            // the second helper could not be started: fan out here
     const auto t2 = now();
     // everything this call queued has completed by now (the helper waited for the last D2H event); these return at once
-    hipError_t e1 = wait_stream(s), e2 = wait_stream(L.copy_st);
+    hipError_t e1 = wait_stream(s), e2 = wait_stream(copy_st);
     if (launch_rc) return launch_rc;
     if (e1 != hipSuccess || e2 != hipSuccess || copy_err) return fail(SRCNN_E_HIP, "pipeline failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     HIP_TRY(hipGetLastError());
@@ -766,11 +763,11 @@ int srcnn_y_path_f32(const float* in, unsigned w, unsigned h, unsigned dw, unsig
     const size_t in_n = (size_t)w * h, out_n = (size_t)dw * dh;
     HostCallBuffers& hb = cx.host_call;
     std::lock_guard<std::mutex> one(hb.mu);
-    if ((rc = grow(hb.d_in, hb.d_in_n, in_n))) return rc;
-    if ((rc = grow(hb.d_out, hb.d_out_n, out_n))) return rc;
-    if ((rc = copy_h2d_any(cx, hb.d_in, in, sizeof(float) * in_n, nullptr))) return rc;
-    if ((rc = srcnn_y_path_f32_dev(hb.d_in, w, h, dw, dh, filter, hb.d_out, nullptr))) return rc;
-    return copy_d2h_any(cx, out, hb.d_out, sizeof(float) * out_n, nullptr);       // same (default) stream: ordered behind the kernels
+    if ((rc = hb.d.in.grow(in_n))) return rc;
+    if ((rc = hb.d.out.grow(out_n))) return rc;
+    if ((rc = copy_h2d_any(cx, hb.d.in.data(), in, sizeof(float) * in_n, nullptr))) return rc;
+    if ((rc = srcnn_y_path_f32_dev(hb.d.in.data(), w, h, dw, dh, filter, hb.d.out.data(), nullptr))) return rc;
+    return copy_d2h_any(cx, out, hb.d.out.data(), sizeof(float) * out_n, nullptr);       // same (default) stream: ordered behind the kernels
 }
 
 int srcnn_y_upscale2x_f32(const float* in, unsigned w, unsigned h, float* out)
@@ -1009,31 +1006,32 @@ int srcnn_y_upscale2x_f32_node_dev(const float* d_in, unsigned w, unsigned h, fl
         if (r) return r;
         std::lock_guard<std::mutex> nlk(cx.node_mu);
         NodeLane& N = cx.node;
-        if (!N.st) HIP_TRY(hipStreamCreateWithFlags(&N.st, hipStreamNonBlocking));
-        if (!N.copy_st) HIP_TRY(hipStreamCreateWithFlags(&N.copy_st, hipStreamNonBlocking));
+        if (!N.st) HIP_TRY(hipStreamCreateWithFlags(N.st.put(), hipStreamNonBlocking));
+        if (!N.copy_st) HIP_TRY(hipStreamCreateWithFlags(N.copy_st.put(), hipStreamNonBlocking));
+        const hipStream_t st = N.st.get(), copy_st = N.copy_st.get();
         unsigned R0 = 0, Rn = 0;
         (void)srcnn_band_rows(dh, (int)k, (int)nctx, &R0, &Rn);          // the same partition the tiled pieces are planned on
         const unsigned R1 = R0 + Rn;
         if (R1 <= R0) return SRCNN_OK;
         std::vector<TableRef> tables;
         Call c;
-        c.cx = &cx; c.s = N.st; c.ws = &N.ws; c.mode = mode; c.hold = &tables;
+        c.cx = &cx; c.s = st; c.ws = &N.ws; c.mode = mode; c.hold = &tables;
         const bool is_root = (&cx == root);
         // source rows of this band, pulled from the root device into a buffer with whole-frame geometry
         unsigned lo = 0, hi = h;
         if ((r = y_path_source_rows(c, h, dh, SRCNN_FILTER_BICUBIC, R0, R1, lo, hi))) return r;
         const float* src = d_in;
         if (!is_root) {
-            if ((r = grow(N.in, N.in_n, (size_t)w * h))) return r;
-            if ((r = grow(N.band, N.band_n, (size_t)(R1 - R0) * dw))) return r;
-            HIP_TRY(hipMemcpyPeerAsync(N.in + (size_t)lo * w, cx.device, d_in + (size_t)lo * w, root->device,
-                                       sizeof(float) * (size_t)(hi - lo) * w, N.st));
-            src = N.in;
+            if ((r = N.in.grow((size_t)w * h))) return r;
+            if ((r = N.band.grow((size_t)(R1 - R0) * dw))) return r;
+            HIP_TRY(hipMemcpyPeerAsync(N.in.data() + (size_t)lo * w, cx.device, d_in + (size_t)lo * w, root->device,
+                                       sizeof(float) * (size_t)(hi - lo) * w, st));
+            src = N.in.data();
         }
         while (N.events.size() < nsub + 2) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, kBlockingEvent));
-            N.events.push_back(e);
+            Event e;
+            HIP_TRY(hipEventCreateWithFlags(e.put(), kBlockingEvent));
+            N.events.push_back(std::move(e));
         }
         // sub-bands: the kernels of sub-band i+1 are queued before the host waits for sub-band i and pushes it to the root
         // on the copy stream, so the push (one xGMI link per peer, all peers concurrently) hides behind compute
@@ -1043,17 +1041,17 @@ int srcnn_y_upscale2x_f32_node_dev(const float* d_in, unsigned w, unsigned h, fl
         while (cut.size() < nsub + 1) cut.push_back(R1);
         auto launch = [&](unsigned i) -> int {
             if (cut[i + 1] <= cut[i]) return SRCNN_OK;
-            float* dst = is_root ? d_out + (size_t)cut[i] * dw : N.band + (size_t)(cut[i] - R0) * dw;
+            float* dst = is_root ? d_out + (size_t)cut[i] * dw : N.band.data() + (size_t)(cut[i] - R0) * dw;
             int q = y_path_range(c, src, w, h, dw, dh, SRCNN_FILTER_BICUBIC, cut[i], cut[i + 1], dst);
             if (q) return q;
-            HIP_TRY(hipEventRecord(N.events[i], N.st));
+            HIP_TRY(hipEventRecord(N.events[i].get(), st));
             return SRCNN_OK;
         };
         auto push = [&](unsigned i) -> int {
             if (is_root || cut[i + 1] <= cut[i]) return SRCNN_OK;
-            HIP_TRY(wait_event(N.events[i]));
-            HIP_TRY(hipMemcpyPeerAsync(d_out + (size_t)cut[i] * dw, root->device, N.band + (size_t)(cut[i] - R0) * dw, cx.device,
-                                       sizeof(float) * (size_t)(cut[i + 1] - cut[i]) * dw, N.copy_st));
+            HIP_TRY(wait_event(N.events[i].get()));
+            HIP_TRY(hipMemcpyPeerAsync(d_out + (size_t)cut[i] * dw, root->device, N.band.data() + (size_t)(cut[i] - R0) * dw, cx.device,
+                                       sizeof(float) * (size_t)(cut[i + 1] - cut[i]) * dw, copy_st));
             return SRCNN_OK;
         };
         if ((r = launch(0))) return r;
@@ -1062,10 +1060,10 @@ int srcnn_y_upscale2x_f32_node_dev(const float* d_in, unsigned w, unsigned h, fl
             if ((r = push(i))) return r;
         }
         // wait for both queues by polling their events (8 workers inside hipStreamSynchronize would hold 8 host cores)
-        HIP_TRY(hipEventRecord(N.events[nsub], N.st));
-        HIP_TRY(hipEventRecord(N.events[nsub + 1], N.copy_st));
-        HIP_TRY(wait_event(N.events[nsub]));
-        HIP_TRY(wait_event(N.events[nsub + 1]));
+        HIP_TRY(hipEventRecord(N.events[nsub].get(), st));
+        HIP_TRY(hipEventRecord(N.events[nsub + 1].get(), copy_st));
+        HIP_TRY(wait_event(N.events[nsub].get()));
+        HIP_TRY(wait_event(N.events[nsub + 1].get()));
         return SRCNN_OK;
     };
     std::vector<std::thread> th(nctx);

@@ -14,7 +14,9 @@
 //     them toggling the timeout to 0 between calls: regions are exclusive, a no-op arm() never releases somebody else's region,
 //     a region that outlives its deadline is marked (under the lock) and aborted exactly once, stale generations are ignored;
 //   * libsrcnn_amd/csrc/srcnn_frame_args.hpp (everything the YUV / packed / RGB frame calls decide before any device lookup:
-//     plane geometry, pitches, alignment, the end-of-plane pointer arithmetic of the overlap rules) on host buffers.
+//     plane geometry, pitches, alignment, the end-of-plane pointer arithmetic of the overlap rules) on host buffers;
+//   * libsrcnn_amd/csrc/srcnn_owned.hpp      (the two owner types every HIP resource of the host layer is a member of) with
+//     malloc-backed traits that count and log their calls: a double or a missing free fails the ASan run by itself.
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -23,6 +25,7 @@
 #include <cstring>
 #include <functional>
 #include <limits>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -31,6 +34,7 @@
 #include "../../include/srcnn_amd_debug.h"
 #include "../../libsrcnn_amd/csrc/resample_table.hpp"
 #include "../../libsrcnn_amd/csrc/srcnn_frame_args.hpp"
+#include "../../libsrcnn_amd/csrc/srcnn_owned.hpp"
 #include "../../libsrcnn_amd/csrc/srcnn_watchdog.hpp"
 
 extern "C" {
@@ -462,6 +466,108 @@ static void check_frame_args()
     }
 }
 
+// ---- the owner types (srcnn_owned.hpp) ----
+static int g_live = 0, g_made = 0, g_destroyed = 0;
+static std::string g_log;                 // 'd' drain, 'f' free, 'a' alloc, in call order
+static bool g_alloc_fails = false;
+struct TestHandleTraits { static void destroy(int* h) { ++g_destroyed; --g_live; free(h); } };
+using TestHandle = srcnn::Owned<int*, TestHandleTraits>;
+static int make_handle(int** out) { *out = static_cast<int*>(malloc(sizeof(int))); **out = ++g_made; ++g_live; return 0; }
+struct TestAlloc {
+    static void drain() { g_log += 'd'; }
+    static int alloc(void** p, size_t bytes, int tag = 0)
+    {
+        g_log += 'a';
+        if (g_alloc_fails) return -7 - tag;
+        *p = malloc(bytes);
+        ++g_live;
+        return 0;
+    }
+    static void free(void* p) { g_log += 'f'; --g_live; ::free(p); }
+};
+using TestBuf = srcnn::GrowBuf<double, TestAlloc>;
+
+static void check_owners()
+{
+    {
+        TestHandle a;
+        CHECK(!a && a.get() == nullptr, "a fresh owner is empty");
+        a.reset();
+        CHECK(make_handle(a.put()) == 0 && a && *a.get() == 1 && g_live == 1, "filled through the out-parameter");
+        TestHandle b(std::move(a));
+        CHECK(!a && b && *b.get() == 1 && g_destroyed == 0, "move-construct transfers, the source reads empty");
+        TestHandle c;
+        c = std::move(b);
+        CHECK(!b && c && *c.get() == 1 && g_destroyed == 0, "move-assign transfers, the source reads empty");
+        TestHandle d;
+        make_handle(d.put());
+        int* const old_c = c.get();
+        c = std::move(d);                                      // over a full owner: handle 1 goes first, handle 2 moves in
+        CHECK(g_destroyed == 1 && g_live == 1 && c.get() != old_c && *c.get() == 2 && !d, "move-assign over a full owner destroys the old handle");
+        TestHandle& self = c;
+        c = std::move(self);
+        CHECK(c && *c.get() == 2 && g_destroyed == 1, "self-move is harmless");
+        int* raw = c.release();
+        CHECK(!c && raw && *raw == 2 && g_destroyed == 1 && g_live == 1, "release() hands the handle out undestroyed");
+        make_handle(c.put());
+        make_handle(c.put());                                  // put() on a full owner destroys what it held
+        CHECK(g_destroyed == 2 && *c.get() == 4, "put() empties first");
+        TestHandleTraits::destroy(raw);
+        c.reset();
+        c.reset();
+        CHECK(g_destroyed == 4 && g_live == 0, "reset() twice is harmless");
+        // a vector that reallocates moves its owners: nothing is destroyed early, everything once at the end
+        std::vector<TestHandle> v;
+        for (int i = 0; i < 100; ++i) { v.emplace_back(); make_handle(v.back().put()); }
+        CHECK(g_destroyed == 4 && g_live == 100, "a reallocating vector destroys nothing early (%d destroyed, %d live)", g_destroyed, g_live);
+        bool in_order = true;
+        for (int i = 0; i < 100; ++i) in_order = in_order && *v[i].get() == 5 + i;
+        CHECK(in_order, "the vector's handles are the ones created");
+    }
+    CHECK(g_live == 0 && g_destroyed == g_made, "every handle destroyed exactly once: %d made, %d destroyed", g_made, g_destroyed);
+    {
+        TestBuf b;
+        CHECK(b.grow(0) == 0 && b.data() == nullptr && b.size() == 0 && g_log.empty(), "grow(0) on an empty buffer does not allocate");
+        CHECK(b.grow(10) == 0 && b.size() == 10 && g_log == "a", "first growth: no drain, no free (%s)", g_log.c_str());
+        double* const p = b.data();
+        p[0] = 1.0; p[9] = 2.0;
+        CHECK(b.grow(9) == 0 && b.grow(10) == 0 && b.data() == p && b.size() == 10 && g_log == "a", "grow-only: a smaller request keeps the block");
+        g_log.clear();
+        CHECK(b.grow(20) == 0 && b.size() == 20 && g_log == "dfa" && g_live == 1, "growth drains, frees, then allocates (%s)", g_log.c_str());
+        b.data()[19] = 3.0;
+        TestBuf c(std::move(b));
+        CHECK(!b.data() && b.size() == 0 && c.size() == 20 && c.data()[19] == 3.0, "move-construct transfers");
+        b = std::move(c);
+        TestBuf& self = b;
+        b = std::move(self);
+        CHECK(!c.data() && c.size() == 0 && b.size() == 20 && b.data()[19] == 3.0 && g_live == 1, "move-assign transfers; self-move is harmless");
+        CHECK(c.grow(5) == 0 && g_live == 2, "a moved-from buffer is an empty one");
+        g_log.clear();
+        c = std::move(b);                                      // over a full buffer: its block is freed first
+        CHECK(g_log == "f" && g_live == 1 && c.size() == 20, "move-assign over a full buffer frees its block (%s)", g_log.c_str());
+        g_alloc_fails = true;
+        g_log.clear();
+        CHECK(c.grow(40, 3) == -10 && c.data() == nullptr && c.size() == 0 && g_log == "dfa" && g_live == 0,
+              "a failed allocation returns the allocator's error and leaves the buffer empty (%s)", g_log.c_str());
+        CHECK(c.grow(40) == -7 && c.data() == nullptr && c.size() == 0, "and again from empty");
+        g_alloc_fails = false;
+        CHECK(c.grow(40) == 0 && c.size() == 40, "the next growth succeeds");
+        c.data()[39] = 4.0;
+        c.reset();
+        c.reset();
+        CHECK(c.data() == nullptr && c.size() == 0 && g_live == 0, "reset() twice is harmless");
+        // emptied by assignment, as srcnn_trim empties the owners of a struct that lives on
+        struct Pair { TestBuf x, y; TestHandle h[2]; } pr;
+        pr.x.grow(3); pr.y.grow(4); make_handle(pr.h[1].put());
+        pr = {};
+        CHECK(g_live == 0 && !pr.x.data() && !pr.y.data() && !pr.h[1], "struct = {} releases every owner in it");
+        std::vector<TestBuf> v;
+        for (int i = 0; i < 50; ++i) { v.emplace_back(); v.back().grow(1 + i); v.back().data()[i] = i; }
+        CHECK(g_live == 50, "a reallocating vector of buffers frees nothing early");
+    }
+    CHECK(g_live == 0, "every block freed: %d live", g_live);
+}
+
 int main()
 {
     check_tables();
@@ -471,6 +577,7 @@ int main()
     check_watchdog();
     check_frame_geometry();
     check_frame_args();
+    check_owners();
     if (g_fail) { fprintf(stderr, "host_sanitize: %d check(s) failed\n", g_fail); return 1; }
     printf("host_sanitize: all checks passed (%d stand-in device calls)\n", g_calls.load());
     return 0;
