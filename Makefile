@@ -6,6 +6,7 @@
 #                      (the reference's install / uninstall: Makefiles/Makefile.linux:64-75)
 #   make install-yuv -> the same + include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h, srcnn_amd_yuv_packed.h (the YUV extensions)
 #   make install-rgb -> the same as install + include/srcnn_amd_rgb.h (RGB(A) images in device memory)
+#   make install-rect -> the same as install + include/srcnn_amd_rect.h (one rectangle of the Y path's output)
 #   make oracle     -> the CPU checker (and oracle/_ref where the reference tree is present)
 #   make test       -> CPU test-suite;  make gpu-test on a gfx950 box
 #   make ubench     -> tools/ubench/bin/* (microbenchmarks; hipcc, gfx950)
@@ -27,12 +28,12 @@ endif
 HIPFLAGS := --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -fvisibility=hidden -Wall \
             -Wno-unused-result -Wno-unused-value -Wno-ignored-attributes -D__HIP_PLATFORM_AMD__ $(STRICT_DEF)
 ifeq ($(STRICT_ONLY),1)
-SRCS    := srcnn_kernels.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_window.hip srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 else
-SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_window.hip srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 endif
 OBJS    := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(basename $(SRCS))))
-HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/libsrcnn_dropin.h
+HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_window.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/srcnn_amd_rect.h include/libsrcnn_dropin.h
 
 PREFIX  ?= /usr/local
 ROCM    ?= /opt/rocm
@@ -131,12 +132,16 @@ install-yuv: install
 install-rgb: install
 	install -m 644 include/srcnn_amd_rgb.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h
 
+# the rect extension header (include/srcnn_amd_rect.h)
+install-rect: install
+	install -m 644 include/srcnn_amd_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect.h
+
 uninstall:
 	rm -f $(DESTDIR)$(PREFIX)/lib/libsrcnn_amd.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.a
-	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h
+	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect.h
 	@if [ -z "$(DESTDIR)" ] && [ "$$(id -u)" = 0 ]; then ldconfig; fi
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) oracle/_build oracle/_ref tests/host/_build tools/ubench/bin
 
-.PHONY: all oracle test gpu-test clean asan tsan ubench install install-yuv install-rgb uninstall
+.PHONY: all oracle test gpu-test clean asan tsan ubench install install-yuv install-rgb install-rect uninstall

@@ -55,7 +55,9 @@ YUV_EX_SYMBOLS = ["srcnn_yuv_ex_abi_version", "srcnn_yuv_plane_size", "srcnn_yuv
 RGB_SYMBOLS = ["srcnn_rgb_abi_version", "srcnn_rgb_plane_size", "srcnn_rgb_upscale_dev"]
 # packed YUV frames (include/srcnn_amd_yuv_packed.h, listed in include/srcnn_amd_yuv_packed.abi; its own version)
 YUV_PACKED_SYMBOLS = ["srcnn_yuv_packed_abi_version", "srcnn_yuv_packed_row_bytes", "srcnn_yuv_packed_upscale_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS   # everything the library exports besides the two C++ symbols
+# one rectangle of the Y path's output (include/srcnn_amd_rect.h, listed in include/srcnn_amd_rect.abi; its own version)
+RECT_SYMBOLS = ["srcnn_rect_abi_version", "srcnn_y_path_rect_source", "srcnn_y_path_rect_f32_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -151,9 +153,12 @@ def lib():
             "srcnn_yuv_packed_abi_version": (i, []),
             "srcnn_yuv_packed_row_bytes": (i, [i, u, C.POINTER(sz), C.POINTER(u)]),
             "srcnn_yuv_packed_upscale_dev": (i, [i, u, u, f, i, vp, sz, vp, sz, vp]),
+            "srcnn_rect_abi_version": (i, []),
+            "srcnn_y_path_rect_source": (i, [u, u, u, u, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
+            "srcnn_y_path_rect_f32_dev": (i, [vp, sz, u, u, u, u, i, u, u, u, u, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -406,6 +411,34 @@ def y_upscale2x_band(y, row0, rows):
     check(lib().srcnn_y_upscale2x_f32_band_dev(din.ptr, w, h, row0, rows, dout.ptr, None))
     sync()
     return dout.to_numpy(np.float32, (rows, 2 * w))
+
+
+def y_path_rect_source(w, h, dw, dh, filt, x0, y0, rw, rh):
+    """(sx0, sy0, sw, sh): the source rectangle output rect [x0, x0 + rw) x [y0, y0 + rh) of the dw x dh Y path depends on
+    (srcnn_y_path_rect_source; no device)."""
+    r = [C.c_uint(0) for _ in range(4)]
+    check(lib().srcnn_y_path_rect_source(int(w), int(h), int(dw), int(dh), int(filt), int(x0), int(y0), int(rw), int(rh),
+                                         *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+def y_path_rect_dev(src, in_pitch, w, h, dw, dh, filt, x0, y0, rw, rh, dst, out_pitch, stream=None):
+    """srcnn_y_path_rect_f32_dev on device memory, as given: src / dst plane arguments (see _addr), pitches in bytes (0 =
+    tight).  Asynchronous on `stream` (a Stream, a raw handle or None); raises SrcnnError with the library's code."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_y_path_rect_f32_dev(_addr(src), int(in_pitch or 0), int(w), int(h), int(dw), int(dh), int(filt), int(x0), int(y0),
+                                          int(rw), int(rh), _addr(dst), int(out_pitch or 0), handle))
+
+
+def y_path_rect(plane, dw, dh, filt, x0, y0, rw, rh):
+    """Samples [x0, x0 + rw) x [y0, y0 + rh) of y_path(plane, dw, dh, filt) through srcnn_y_path_rect_f32_dev: numpy in, numpy out."""
+    y = _plane(plane)
+    h, w = y.shape
+    din = DeviceBuffer.from_numpy(y)
+    dout = DeviceBuffer(max(1, rw * rh * 4))
+    y_path_rect_dev(din, 0, w, h, dw, dh, filt, x0, y0, rw, rh, dout, 0)
+    sync()
+    return dout.to_numpy(np.float32, (rh, rw))
 
 
 def _stage(fn, src, out_shape, *dims):

@@ -25,7 +25,10 @@
 #include <sys/auxv.h>
 #include <unistd.h>
 
+#include "../../include/srcnn_amd_rect.h"
+#include "srcnn_frame_args.hpp"
 #include "srcnn_host.hpp"
+#include "srcnn_window.h"
 
 namespace srcnn {
 
@@ -872,6 +875,55 @@ int resample_src_rows(Call& c, const YSource& src, unsigned sw, unsigned sh, uns
     return SRCNN_OK;
 }
 
+// Columns [c0,c1) x rows [r0,r1) of what resample_src_rows produces for a float plane, bit for bit, at the cost of that window:
+// d_dst is tight (c1 - c0 floats per row), the source has in_stride floats per row.  Same pass order, same skipped passes
+// and the same identity copy as above; the intermediate image (fp32, like the reference's) covers only the source span the
+// contribution tables give for the window.  The generic one-sample-per-thread kernels serve every shape: k_rs2d computes the
+// same bits (tests/test_gpu_resample_dispatch.py), so no dispatch is needed for parity.
+int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned sw, unsigned sh, unsigned dw, unsigned dh, int filter,
+                    unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst)
+{
+    Workspace& ws = *c.ws;
+    hipStream_t s = c.s;
+    const int nc = (int)(c1 - c0), nr = (int)(r1 - r0);
+    if (sw == dw && sh == dh) {      // the pinned identity-size deviation: the window is copied
+        launch_window_copy(d_in + (size_t)r0 * in_stride + c0, in_stride, d_dst, (size_t)nc, nc, nr, s);
+        return SRCNN_OK;
+    }
+    TableRef tv, th;
+    int rc;
+    if (sw != dw && (rc = get_table(c, filter, dw, sw, th))) return rc;
+    if (sh != dh && (rc = get_table(c, filter, dh, sh, tv))) return rc;
+    if (!tv) {                       // rows keep their size: the horizontal pass alone
+        launch_window_rows(d_in + (size_t)r0 * in_stride, in_stride, 0, d_dst, (int)c0, nc, nr, view_of(th), s);
+        return SRCNN_OK;
+    }
+    if (!th) {                       // columns keep their size: the vertical pass alone
+        launch_window_cols(d_in + c0, in_stride, 0, d_dst, nc, (int)r0, nr, view_of(tv), s);
+        return SRCNN_OK;
+    }
+    if (dw <= sw) {
+        // horizontal first, over the source rows the vertical taps of rows [r0, r1) read, then vertical
+        unsigned lo = 0, hi = sh;
+        tv->source_span(r0, r1, lo, hi);
+        hi = std::min(hi, sh);
+        if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for rows [%u,%u)", r0, r1);
+        if ((rc = ws.grow(ws.tmp, (size_t)nc * (hi - lo)))) return rc;
+        launch_window_rows(d_in + (size_t)lo * in_stride, in_stride, 0, ws.tmp.data(), (int)c0, nc, (int)(hi - lo), view_of(th), s);
+        launch_window_cols(ws.tmp.data(), (size_t)nc, (int)lo, d_dst, nc, (int)r0, nr, view_of(tv), s);
+    } else {
+        // vertical first, over the source columns the horizontal taps of columns [c0, c1) read, then horizontal
+        unsigned lo = 0, hi = sw;
+        th->source_span(c0, c1, lo, hi);
+        hi = std::min(hi, sw);
+        if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for columns [%u,%u)", c0, c1);
+        if ((rc = ws.grow(ws.tmp, (size_t)(hi - lo) * nr))) return rc;
+        launch_window_cols(d_in + lo, in_stride, 0, ws.tmp.data(), (int)(hi - lo), (int)r0, nr, view_of(tv), s);
+        launch_window_rows(ws.tmp.data(), (size_t)(hi - lo), (int)lo, d_dst, (int)c0, nc, nr, view_of(th), s);
+    }
+    return SRCNN_OK;
+}
+
 }  // namespace
 
 int resample_rows_range(Call& c, const float* d_in, unsigned sw, unsigned sh, unsigned dw, unsigned dh, int filter,
@@ -1031,6 +1083,92 @@ int y_path_range(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw
 int y_path_frame(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, float* d_out)
 {
     return y_path_range(c, d_in, w, h, dw, dh, filter, 0, dh, d_out);
+}
+
+namespace {
+
+// Output samples [x0,x1) x [r0,r1) in one pass.  A pixel's arithmetic does not depend on where its tile lies, so a window of
+// the upscaled plane goes through the unchanged layer kernels as if it were a Ww-wide frame of dh rows: columns [uax,ubx) =
+// the rect + 2 (layer 3) + 4 (layer 1), cut short at the true borders.  The kernels' clamp-to-edge is then wrong only inside
+// that halo, which the store leaves behind; where the window ends at a true border the clamp is the frame's own.  Rows are
+// handled as y_path_rows handles them (H and the row bases are the true ones).
+int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                     unsigned x0, unsigned x1, unsigned r0, unsigned r1, float* d_out, size_t out_stride)
+{
+    Workspace& ws = *c.ws;
+    [[maybe_unused]] Ctx& cx = *c.cx;
+    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
+    const unsigned uax = cax >= 4 ? cax - 4 : 0, ubx = std::min(dw, cbx + 4);
+    const unsigned Ww = ubx - uax;
+    const unsigned ca = r0 >= 2 ? r0 - 2 : 0, cb = std::min(dh, r1 + 2);
+    const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dh, cb + 4);
+    int rc;
+    if ((rc = ws.grow(ws.up, (size_t)Ww * (ub - ua)))) return rc;
+    if ((rc = ws.grow(ws.win, (size_t)Ww * (r1 - r0)))) return rc;
+    const float* interior = ws.win.data() + (x0 - uax);
+#ifndef SRCNN_STRICT_ONLY
+    if (c.mode == SRCNN_MODE_FAST_F16) {
+        {
+            StageTimer t(SRCNN_STAGE_RESAMPLE, c);
+            if ((rc = resample_window(c, d_in, in_stride, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
+        }
+        {
+            StageTimer t(SRCNN_STAGE_CONV12, c);
+            launch_fused_f16(ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.win.data(), (int)r0, (int)(r1 - r0), cx.fused_w.data(),
+                             cx.num_cus, c.s);
+        }
+        launch_window_copy(interior, Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s);
+        HIP_TRY(hipGetLastError());
+        return SRCNN_OK;
+    }
+#endif
+    if ((rc = ws.grow(ws.c2, (size_t)C2N * Ww * (cb - ca)))) return rc;
+    TraceRange tr("srcnn y_path rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, r0, r1, dw, dh);
+    {
+        StageTimer t(SRCNN_STAGE_RESAMPLE, c);
+        if ((rc = resample_window(c, d_in, in_stride, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
+    }
+    const size_t plane = (size_t)Ww * (cb - ca);
+    {
+        StageTimer t(SRCNN_STAGE_CONV12, c);
+        run_conv12(c, ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
+    }
+    {
+        StageTimer t(SRCNN_STAGE_CONV3, c);
+        launch_conv3(ws.c2.data(), plane, (int)Ww, (int)dh, (int)ca, (int)(cb - ca), ws.win.data(), (int)r0, (int)(r1 - r0), c.relax(), c.s);
+    }
+    launch_window_copy(interior, Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s);      // (outside the stage timers)
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+        ws.queue_dirty = true;
+        return fail(SRCNN_E_HIP, "y_path_rect: %s", hipGetErrorString(e));
+    }
+    return SRCNN_OK;
+}
+
+}  // namespace
+
+// The rect [x0,x1) x [y0,y1).  A rect that is a row range of tight planes is one (y_path_range); every other is produced from
+// windows, in row bands when the 32 layer-2 planes of the window would exceed the workspace budget -- with identical bits.
+int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride)
+{
+    if (x1 > dw || x0 >= x1 || y1 > dh || y0 >= y1) return fail(SRCNN_E_ARG, "rect [%u,%u)x[%u,%u) outside %ux%u", x0, x1, y0, y1, dw, dh);
+    if (dh > (1u << 20) || h > (1u << 20) || dw > 0x7fffffu || (y1 - y0) > 65535u * 16u)
+        return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
+    if (x0 == 0 && x1 == dw && in_stride == w && out_stride == dw) return y_path_range(c, d_in, w, h, dw, dh, filter, y0, y1, d_out);
+    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
+    const unsigned Ww = std::min(dw, cbx + 4) - (cax >= 4 ? cax - 4 : 0);
+    const size_t row_bytes = (size_t)C2N * Ww * sizeof(float);
+    const bool no_planes = c.mode == SRCNN_MODE_FAST_F16;      // the fused kernel has no layer-2 planes
+    if (no_planes || row_bytes * ((size_t)(y1 - y0) + 4) <= G.ws_budget.load())
+        return y_path_rect_rows(c, d_in, in_stride, w, h, dw, dh, filter, x0, x1, y0, y1, d_out, out_stride);
+    const unsigned band = budget_band_rows(Ww);
+    for (unsigned a = y0; a < y1; a += band) {
+        const unsigned b = std::min(y1, a + band);
+        int rc = y_path_rect_rows(c, d_in, in_stride, w, h, dw, dh, filter, x0, x1, a, b, d_out + (size_t)(a - y0) * out_stride, out_stride);
+        if (rc) return rc;
+    }
+    return SRCNN_OK;
 }
 
 int check_y_path_args(const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const float* d_out)
@@ -1440,6 +1578,80 @@ int srcnn_y_upscale2x_f32_band_dev(const float* d_in, unsigned w, unsigned h, un
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
     return y_path_range(sc.c, d_in, w, h, 2 * w, 2 * h, SRCNN_FILTER_BICUBIC, row0, row0 + rows, d_out_band);
+}
+
+// ---- one rectangle of the output (include/srcnn_amd_rect.h) --------------------------------------
+namespace {
+
+// [lo,hi) of the source axis that destination indices [a,b) of the resampled axis read: the taps of the range, read off the
+// table; an axis that keeps its size is copied
+void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
+{
+    if (dst_len == src_len) { lo = a; hi = b; return; }
+    const AxisTable t = build_axis_table(filter, dst_len, src_len);
+    int l = 0x7fffffff, e = 0;
+    for (unsigned u = a; u < b; ++u) { l = std::min(l, (int)t.first[u]); e = std::max(e, (int)(t.first[u] + t.taps[u])); }
+    lo = (unsigned)l;
+    hi = std::min((unsigned)e, src_len);
+}
+
+// what both rect entry points refuse about the geometry, in the order the header gives
+int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
+{
+    if (w == 0 || h == 0 || rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "zero dimension (%ux%u, rect %ux%u)", w, h, rw, rh);
+    if (dw == 0 || dh == 0) return fail(SRCNN_E_SCALE, "scaled size %ux%u", dw, dh);
+    if (filter < 0 || filter > 4) return fail(SRCNN_E_ARG, "bad filter %d", filter);
+    if ((unsigned long long)x0 + rw > dw || (unsigned long long)y0 + rh > dh)
+        return fail(SRCNN_E_ARG, "rect %ux%u at (%u,%u) is not inside the %ux%u output", rw, rh, x0, y0, dw, dh);
+    return SRCNN_OK;
+}
+
+int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned rh)
+{
+    if (h > (1u << 20) || dh > (1u << 20) || dw > 0x7fffffu || rh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL)
+        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
+    return SRCNN_OK;
+}
+
+}  // namespace
+
+int srcnn_rect_abi_version(void) { return SRCNN_AMD_RECT_VERSION; }
+
+int srcnn_y_path_rect_source(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw,
+                             unsigned rh, unsigned* sx0, unsigned* sy0, unsigned* sw, unsigned* sh)
+{
+    int rc;
+    if ((rc = check_rect_geometry(w, h, dw, dh, filter, x0, y0, rw, rh))) return rc;
+    if ((rc = check_rect_limits(w, h, dw, dh, rh))) return rc;
+    const unsigned x1 = x0 + rw, y1 = y0 + rh;
+    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
+    const unsigned uax = cax >= 4 ? cax - 4 : 0, ubx = std::min(dw, cbx + 4);
+    const unsigned cay = y0 >= 2 ? y0 - 2 : 0, cby = std::min(dh, y1 + 2);
+    const unsigned uay = cay >= 4 ? cay - 4 : 0, uby = std::min(dh, cby + 4);
+    unsigned lx, hx, ly, hy;
+    axis_source_span(filter, dw, w, uax, ubx, lx, hx);
+    axis_source_span(filter, dh, h, uay, uby, ly, hy);
+    if (sx0) *sx0 = lx;
+    if (sy0) *sy0 = ly;
+    if (sw) *sw = hx - lx;
+    if (sh) *sh = hy - ly;
+    return SRCNN_OK;
+}
+
+int srcnn_y_path_rect_f32_dev(const float* d_in, size_t in_pitch, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                              unsigned x0, unsigned y0, unsigned rw, unsigned rh, float* d_out, size_t out_pitch, void* stream)
+{
+    int rc;
+    if (!d_in || !d_out) return fail(SRCNN_E_ARG, "NULL pointer");
+    if ((rc = check_rect_geometry(w, h, dw, dh, filter, x0, y0, rw, rh))) return rc;
+    YuvPlane in, out;
+    if ((rc = describe_plane(in, d_in, in_pitch, sizeof(float) * (size_t)w, h, 4, "input", 0))) return rc;
+    if ((rc = describe_plane(out, d_out, out_pitch, sizeof(float) * (size_t)rw, rh, 4, "output", 0))) return rc;
+    if ((rc = check_rect_limits(w, h, dw, dh, rh))) return rc;
+    if ((rc = check_in_out_overlap(&in, 1, &out, 1))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    return y_path_rect(sc.c, d_in, in.pitch / sizeof(float), w, h, dw, dh, filter, x0, y0, x0 + rw, y0 + rh, d_out, out.pitch / sizeof(float));
 }
 
 // ---- per-kernel timing -------------------------------------------------------------------------

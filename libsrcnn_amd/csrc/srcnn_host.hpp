@@ -93,8 +93,9 @@ struct Scratch {            // the buffers of a Workspace: movable, so that a wo
     DevBuf<float> up;       // upscaled Y (band)
     DevBuf<float> c2;       // 32 layer-2 planes (band)
     DevBuf<float> planes;   // colour shell: split planes / Y' / resized chroma planes
+    DevBuf<float> win;      // rect call: the layer-3 result of a window (band), tight, before its interior is stored
     DevBuf<unsigned char> bytes;
-    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size()) + bytes.size(); }
+    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size() + win.size()) + bytes.size(); }
 };
 struct Workspace : Scratch {          // scratch of one stream / graph / lane; grow-only
     std::mutex mu;          // held while a call enqueues work that uses this scratch
@@ -309,6 +310,10 @@ int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw
 int y_path_range(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
                  unsigned r0, unsigned r1, float* d_out);
 int y_path_frame(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, float* d_out);
+// Output samples [x0,x1) x [y0,y1) of the (dw x dh) result only, at the cost of a window around them.  in_stride / out_stride
+// are in floats; d_out is where sample (x0, y0) goes.
+int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride);
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);
 // rows of layer-2 scratch one band may hold under the workspace budget (>= 16), for a dw-wide output
