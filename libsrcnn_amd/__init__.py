@@ -57,7 +57,9 @@ RGB_SYMBOLS = ["srcnn_rgb_abi_version", "srcnn_rgb_plane_size", "srcnn_rgb_upsca
 YUV_PACKED_SYMBOLS = ["srcnn_yuv_packed_abi_version", "srcnn_yuv_packed_row_bytes", "srcnn_yuv_packed_upscale_dev"]
 # one rectangle of the Y path's output (include/srcnn_amd_rect.h, listed in include/srcnn_amd_rect.abi; its own version)
 RECT_SYMBOLS = ["srcnn_rect_abi_version", "srcnn_y_path_rect_source", "srcnn_y_path_rect_f32_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
+# one rectangle of an RGB(A) image (include/srcnn_amd_rgb_rect.h, listed in include/srcnn_amd_rgb_rect.abi; its own version)
+RGB_RECT_SYMBOLS = ["srcnn_rgb_rect_abi_version", "srcnn_rgb_rect_source", "srcnn_rgb_upscale_rect_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -156,9 +158,13 @@ def lib():
             "srcnn_rect_abi_version": (i, []),
             "srcnn_y_path_rect_source": (i, [u, u, u, u, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
             "srcnn_y_path_rect_f32_dev": (i, [vp, sz, u, u, u, u, i, u, u, u, u, vp, sz, vp]),
+            "srcnn_rgb_rect_abi_version": (i, []),
+            "srcnn_rgb_rect_source": (i, [u, u, f, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
+            "srcnn_rgb_upscale_rect_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), u, u, u, u,
+                                               C.POINTER(vp), C.POINTER(sz), vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -762,6 +768,69 @@ def rgb_upscale(image, multiply=2.0, filt=SRCNNF_Bicubic, layout=None, order="rg
     return out, (dconv.to_numpy(dt, (dh, dw)) if want_conv else None)
 
 
+def rgb_rect_source(w, h, multiply, filt, x0, y0, rw, rh):
+    """(sx0, sy0, sw, sh): the rectangle of the w x h source image that output rect [x0, x0 + rw) x [y0, y0 + rh) of
+    rgb_upscale_dev(..., multiply, filt) depends on (srcnn_rgb_rect_source; no device)."""
+    r = [C.c_uint(0) for _ in range(4)]
+    check(lib().srcnn_rgb_rect_source(int(w), int(h), float(np.float32(multiply)), int(filt), int(x0), int(y0), int(rw), int(rh),
+                                      *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+def rgb_upscale_rect_dev(fmt, w, h, multiply, filt, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, dst_conv=None, dst_conv_pitch=0,
+                         stream=None):
+    """srcnn_rgb_upscale_rect_dev on device memory, as given: the arguments of rgb_upscale_dev with the rect (x0, y0, rw, rh)
+    in output coordinates; src is the whole image, dst / dst_conv are rw x rh images (or the address of pixel (x0, y0) of a
+    full-size image with that image's pitch).  Asynchronous on `stream`; raises SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    four = lambda xs, fill: list(xs) + [fill] * (4 - len(xs))   # noqa: E731
+    s = (vp * 4)(*[_addr(p) for p in four(src, None)]) if src is not None else None
+    d = (vp * 4)(*[_addr(p) for p in four(dst, None)]) if dst is not None else None
+    sp = (sz * 4)(*four(src_pitch, 0)) if src_pitch is not None else None
+    dp = (sz * 4)(*four(dst_pitch, 0)) if dst_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_rgb_upscale_rect_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)),
+                                           int(filt), s, sp, int(x0), int(y0), int(rw), int(rh), d, dp, _addr(dst_conv),
+                                           int(dst_conv_pitch), handle))
+
+
+def rgb_upscale_rect(image, rect, multiply=2.0, filt=SRCNNF_Bicubic, layout=None, order="rgb", depth=None, want_conv=False,
+                     stream=None):
+    """Pixels rect = (x0, y0, rw, rh) of rgb_upscale(image, ...) through srcnn_rgb_upscale_rect_dev: numpy in, numpy out.
+    Returns (out, conv | None), out shaped (rh, rw, c) or (c, rh, rw) like the input."""
+    image = np.asarray(image)
+    if image.ndim != 3:
+        raise ValueError("an RGB(A) image is (h, w, c) or (c, h, w), not %r" % (image.shape,))
+    if layout is None:
+        layout = "interleaved" if image.shape[2] in (3, 4) else "planar"
+    planar = _RGB_LAYOUTS.get(layout.lower() if isinstance(layout, str) else layout, layout) == RGB_PLANAR
+    if depth is None:
+        depth = 8 if image.dtype == np.uint8 else 16
+    dt = np.uint8 if depth == 8 else np.uint16
+    image = np.ascontiguousarray(image, dt)
+    (c, h, w) = image.shape if planar else (image.shape[2], image.shape[0], image.shape[1])
+    if c not in (3, 4):
+        raise ValueError("%d channels: an RGB(A) image has 3 or 4" % c)
+    x0, y0, rw, rh = (int(v) for v in rect)
+    fmt = rgb_format(RGB_PLANAR if planar else RGB_INTERLEAVED, order, c == 4, depth)
+    bps = np.dtype(dt).itemsize
+    din = DeviceBuffer.from_numpy(image)
+    dout = DeviceBuffer(max(1, rw * rh * c * bps))
+    dconv = DeviceBuffer(max(1, rw * rh * bps)) if want_conv else None
+    if planar:
+        src = [(din, k * w * h * bps) for k in range(c)]
+        dst = [(dout, k * rw * rh * bps) for k in range(c)]
+    else:
+        src, dst = [din], [dout]
+    rgb_upscale_rect_dev(fmt, w, h, multiply, filt, src, None, x0, y0, rw, rh, dst, None, dconv, 0, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    out = dout.to_numpy(dt, (c, rh, rw) if planar else (rh, rw, c))
+    return out, (dconv.to_numpy(dt, (rh, rw)) if want_conv else None)
+
+
 def _one_hip_runtime():
     """torch wheels carry a HIP runtime of their own.  When torch is imported first this library binds to that copy and both
     share one runtime; the other way round the process holds two, and memory of one is unknown to the other."""
@@ -787,9 +856,32 @@ def rgb_upscale_torch(t, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=False, ord
     plane with want_conv) is allocated by torch on the same device, in the same layout; the call is queued on
     torch.cuda.current_stream() and neither copies to the host nor synchronises.  Returns (out, conv | None).
     The tensor's device must be the device of the calling thread's current srcnn context."""
+    W, H, Cn, bps, depth, hwc, layout, sh, sc = _rgb_torch_layout(t, depth, "rgb_upscale_torch")
+    import torch
+    _rgb_torch_context(t)
+    dw, dh = output_size(W, H, multiply)
+    if layout == RGB_INTERLEAVED:
+        out = torch.empty((dh, dw, Cn), dtype=t.dtype, device=t.device)
+        src, dst = [t.data_ptr()], [out.data_ptr()]
+        result = out if hwc else out.permute(2, 0, 1)
+    else:
+        out = torch.empty((Cn, dh, dw), dtype=t.dtype, device=t.device)
+        src = [t.data_ptr() + k * sc * bps for k in range(Cn)]
+        dst = [out.data_ptr() + k * dh * dw * bps for k in range(Cn)]
+        result = out.permute(1, 2, 0) if hwc else out
+    conv = torch.empty((dh, dw), dtype=t.dtype, device=t.device) if want_conv else None
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    rgb_upscale_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), dst, None,
+                    conv.data_ptr() if want_conv else None, 0, stream or None)
+    return result, conv
+
+
+def _rgb_torch_layout(t, depth, who):
+    """What the RGB(A) torch calls read off a tensor: (W, H, C, bytes per sample, depth, channels-last shape?, SRCNN_RGB_* layout,
+    row stride, channel stride), strides in samples; ValueError for anything that is not an RGB(A) image in GPU memory."""
     import torch
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError("rgb_upscale_torch needs a torch tensor on a GPU")
+        raise ValueError("%s needs a torch tensor on a GPU" % who)
     sixteen = [torch.int16] + ([torch.uint16] if hasattr(torch, "uint16") else [])
     if t.dtype != torch.uint8 and t.dtype not in sixteen:
         raise ValueError("dtype %s: torch.uint8 or a 16-bit integer type" % (t.dtype,))
@@ -815,6 +907,12 @@ def rgb_upscale_torch(t, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=False, ord
     if lay is None:
         raise ValueError("shape %r with strides %r is neither interleaved pixels nor one plane per channel" % (tuple(t.shape), t.stride()))
     hwc, layout, H, W, Cn, sh, sc = lay
+    return W, H, Cn, bps, depth, hwc, layout, sh, sc
+
+
+def _rgb_torch_context(t):
+    """Load the library beside torch's HIP runtime and make sure the current srcnn context is on the tensor's device."""
+    import torch
     lib()
     _one_hip_runtime()
     dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
@@ -823,20 +921,49 @@ def rgb_upscale_torch(t, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=False, ord
     have = lib().srcnn_context_device(lib().srcnn_get_context())
     if have != dev:
         raise ValueError("the tensor lives on device %d, the current srcnn context on device %d (set_context)" % (dev, have))
+    return dev
+
+
+def rgb_upscale_rect_torch(t, rect, multiply=2.0, filt=SRCNNF_Bicubic, want_conv=False, order="rgb", depth=None, out=None):
+    """srcnn_rgb_upscale_rect_dev on a torch tensor that lives on a GPU: pixels rect = (x0, y0, rw, rh) of what
+    rgb_upscale_torch(t, ...) returns, at the cost of the rect.  t as for rgb_upscale_torch.  out=None: a new tensor of rw x rh
+    pixels in t's layout.  out = a full-size dw x dh image tensor of t's dtype, shape order and memory layout (rows may be
+    padded): the rect is written in place through its strides, nothing else of it is touched, and the view of the rect is
+    returned.  Queued on torch.cuda.current_stream(); returns (rect tensor, conv | None), conv a new rh x rw tensor."""
+    W, H, Cn, bps, depth, hwc, layout, sh, sc = _rgb_torch_layout(t, depth, "rgb_upscale_rect_torch")
+    import torch
+    _rgb_torch_context(t)
+    x0, y0, rw, rh = (int(v) for v in rect)
     dw, dh = output_size(W, H, multiply)
-    if layout == RGB_INTERLEAVED:
-        out = torch.empty((dh, dw, Cn), dtype=t.dtype, device=t.device)
-        src, dst = [t.data_ptr()], [out.data_ptr()]
-        result = out if hwc else out.permute(2, 0, 1)
+    if rw <= 0 or rh <= 0 or x0 < 0 or y0 < 0 or x0 + rw > dw or y0 + rh > dh:
+        raise ValueError("rect %r is not inside the %d x %d output" % ((x0, y0, rw, rh), dw, dh))
+    src = [t.data_ptr()] if layout == RGB_INTERLEAVED else [t.data_ptr() + k * sc * bps for k in range(Cn)]
+    if out is None:
+        if layout == RGB_INTERLEAVED:
+            buf = torch.empty((rh, rw, Cn), dtype=t.dtype, device=t.device)
+            dst, dpitch = [buf.data_ptr()], None
+            result = buf if hwc else buf.permute(2, 0, 1)
+        else:
+            buf = torch.empty((Cn, rh, rw), dtype=t.dtype, device=t.device)
+            dst, dpitch = [buf.data_ptr() + k * rh * rw * bps for k in range(Cn)], None
+            result = buf.permute(1, 2, 0) if hwc else buf
     else:
-        out = torch.empty((Cn, dh, dw), dtype=t.dtype, device=t.device)
-        src = [t.data_ptr() + k * sc * bps for k in range(Cn)]
-        dst = [out.data_ptr() + k * dh * dw * bps for k in range(Cn)]
-        result = out.permute(1, 2, 0) if hwc else out
-    conv = torch.empty((dh, dw), dtype=t.dtype, device=t.device) if want_conv else None
+        if not isinstance(out, torch.Tensor) or out.device != t.device or out.dtype != t.dtype:
+            raise ValueError("out must be a tensor of %s on %s" % (t.dtype, t.device))
+        oW, oH, oC, _, _, ohwc, olayout, osh, osc = _rgb_torch_layout(out, depth, "rgb_upscale_rect_torch(out=)")
+        if (oW, oH, oC, ohwc, olayout) != (dw, dh, Cn, hwc, layout):
+            raise ValueError("out is %d x %d x %d (%s), the output image %d x %d x %d in the layout of t" %
+                             (oW, oH, oC, "interleaved" if olayout == RGB_INTERLEAVED else "planar", dw, dh, Cn))
+        if layout == RGB_INTERLEAVED:
+            dst = [out.data_ptr() + (y0 * osh + x0 * Cn) * bps]
+        else:
+            dst = [out.data_ptr() + (k * osc + y0 * osh + x0) * bps for k in range(Cn)]
+        dpitch = [osh * bps] * len(dst)
+        result = out[y0:y0 + rh, x0:x0 + rw, :] if hwc else out[:, y0:y0 + rh, x0:x0 + rw]
+    conv = torch.empty((rh, rw), dtype=t.dtype, device=t.device) if want_conv else None
     stream = torch.cuda.current_stream(t.device).cuda_stream
-    rgb_upscale_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), dst, None,
-                    conv.data_ptr() if want_conv else None, 0, stream or None)
+    rgb_upscale_rect_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), x0, y0, rw, rh,
+                         dst, dpitch, conv.data_ptr() if want_conv else None, 0, stream or None)
     return result, conv
 
 

@@ -875,19 +875,22 @@ int resample_src_rows(Call& c, const YSource& src, unsigned sw, unsigned sh, uns
     return SRCNN_OK;
 }
 
+}  // namespace
+
 // Columns [c0,c1) x rows [r0,r1) of what resample_src_rows produces for a float plane, bit for bit, at the cost of that window:
 // d_dst is tight (c1 - c0 floats per row), the source has in_stride floats per row.  Same pass order, same skipped passes
 // and the same identity copy as above; the intermediate image (fp32, like the reference's) covers only the source span the
 // contribution tables give for the window.  The generic one-sample-per-thread kernels serve every shape: k_rs2d computes the
-// same bits (tests/test_gpu_resample_dispatch.py), so no dispatch is needed for parity.
-int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned sw, unsigned sh, unsigned dw, unsigned dh, int filter,
-                    unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst)
+// same bits (tests/test_gpu_resample_dispatch.py), so no dispatch is needed for parity.  d_in may itself be a window of the
+// sw x sh plane: its first float is sample (in_x0, in_y0), and it holds every sample the taps of the window read.
+int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned sw, unsigned sh,
+                    unsigned dw, unsigned dh, int filter, unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst)
 {
     Workspace& ws = *c.ws;
     hipStream_t s = c.s;
     const int nc = (int)(c1 - c0), nr = (int)(r1 - r0);
     if (sw == dw && sh == dh) {      // the pinned identity-size deviation: the window is copied
-        launch_window_copy(d_in + (size_t)r0 * in_stride + c0, in_stride, d_dst, (size_t)nc, nc, nr, s);
+        launch_window_copy(d_in + (size_t)(r0 - in_y0) * in_stride + (c0 - in_x0), in_stride, d_dst, (size_t)nc, nc, nr, s);
         return SRCNN_OK;
     }
     TableRef tv, th;
@@ -895,11 +898,11 @@ int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned sw, u
     if (sw != dw && (rc = get_table(c, filter, dw, sw, th))) return rc;
     if (sh != dh && (rc = get_table(c, filter, dh, sh, tv))) return rc;
     if (!tv) {                       // rows keep their size: the horizontal pass alone
-        launch_window_rows(d_in + (size_t)r0 * in_stride, in_stride, 0, d_dst, (int)c0, nc, nr, view_of(th), s);
+        launch_window_rows(d_in + (size_t)(r0 - in_y0) * in_stride, in_stride, (int)in_x0, d_dst, (int)c0, nc, nr, view_of(th), s);
         return SRCNN_OK;
     }
     if (!th) {                       // columns keep their size: the vertical pass alone
-        launch_window_cols(d_in + c0, in_stride, 0, d_dst, nc, (int)r0, nr, view_of(tv), s);
+        launch_window_cols(d_in + (c0 - in_x0), in_stride, (int)in_y0, d_dst, nc, (int)r0, nr, view_of(tv), s);
         return SRCNN_OK;
     }
     if (dw <= sw) {
@@ -909,7 +912,7 @@ int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned sw, u
         hi = std::min(hi, sh);
         if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for rows [%u,%u)", r0, r1);
         if ((rc = ws.grow(ws.tmp, (size_t)nc * (hi - lo)))) return rc;
-        launch_window_rows(d_in + (size_t)lo * in_stride, in_stride, 0, ws.tmp.data(), (int)c0, nc, (int)(hi - lo), view_of(th), s);
+        launch_window_rows(d_in + (size_t)(lo - in_y0) * in_stride, in_stride, (int)in_x0, ws.tmp.data(), (int)c0, nc, (int)(hi - lo), view_of(th), s);
         launch_window_cols(ws.tmp.data(), (size_t)nc, (int)lo, d_dst, nc, (int)r0, nr, view_of(tv), s);
     } else {
         // vertical first, over the source columns the horizontal taps of columns [c0, c1) read, then horizontal
@@ -918,13 +921,11 @@ int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned sw, u
         hi = std::min(hi, sw);
         if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for columns [%u,%u)", c0, c1);
         if ((rc = ws.grow(ws.tmp, (size_t)(hi - lo) * nr))) return rc;
-        launch_window_cols(d_in + lo, in_stride, 0, ws.tmp.data(), (int)(hi - lo), (int)r0, nr, view_of(tv), s);
+        launch_window_cols(d_in + (lo - in_x0), in_stride, (int)in_y0, ws.tmp.data(), (int)(hi - lo), (int)r0, nr, view_of(tv), s);
         launch_window_rows(ws.tmp.data(), (size_t)(hi - lo), (int)lo, d_dst, (int)c0, nc, nr, view_of(th), s);
     }
     return SRCNN_OK;
 }
-
-}  // namespace
 
 int resample_rows_range(Call& c, const float* d_in, unsigned sw, unsigned sh, unsigned dw, unsigned dh, int filter,
                         unsigned r0, unsigned r1, float* d_dst)
@@ -1091,9 +1092,11 @@ namespace {
 // the upscaled plane goes through the unchanged layer kernels as if it were a Ww-wide frame of dh rows: columns [uax,ubx) =
 // the rect + 2 (layer 3) + 4 (layer 1), cut short at the true borders.  The kernels' clamp-to-edge is then wrong only inside
 // that halo, which the store leaves behind; where the window ends at a true border the clamp is the frame's own.  Rows are
-// handled as y_path_rows handles them (H and the row bases are the true ones).
-int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
-                     unsigned x0, unsigned x1, unsigned r0, unsigned r1, float* d_out, size_t out_stride)
+// handled as y_path_rows handles them (H and the row bases are the true ones).  (in_x0, in_y0): the sample of the w x h plane
+// at which d_in begins.
+int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned w, unsigned h,
+                     unsigned dw, unsigned dh, int filter, unsigned x0, unsigned x1, unsigned r0, unsigned r1, float* d_out,
+                     size_t out_stride)
 {
     Workspace& ws = *c.ws;
     [[maybe_unused]] Ctx& cx = *c.cx;
@@ -1110,7 +1113,7 @@ int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned w, u
     if (c.mode == SRCNN_MODE_FAST_F16) {
         {
             StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-            if ((rc = resample_window(c, d_in, in_stride, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
+            if ((rc = resample_window(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
         }
         {
             StageTimer t(SRCNN_STAGE_CONV12, c);
@@ -1126,7 +1129,7 @@ int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned w, u
     TraceRange tr("srcnn y_path rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, r0, r1, dw, dh);
     {
         StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-        if ((rc = resample_window(c, d_in, in_stride, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
+        if ((rc = resample_window(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
     }
     const size_t plane = (size_t)Ww * (cb - ca);
     {
@@ -1149,26 +1152,39 @@ int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned w, u
 
 // The rect [x0,x1) x [y0,y1).  A rect that is a row range of tight planes is one (y_path_range); every other is produced from
 // windows, in row bands when the 32 layer-2 planes of the window would exceed the workspace budget -- with identical bits.
-int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
-                unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride)
+// d_in begins at sample (in_x0, in_y0) of the w x h plane and holds at least what the rect depends on; whole_plane: it holds all
+// h rows (the row-range path reads through the frame resamplers, which are not bounded by the rect's source rectangle).
+int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned w, unsigned h, unsigned dw,
+                unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride, bool whole_plane)
 {
     if (x1 > dw || x0 >= x1 || y1 > dh || y0 >= y1) return fail(SRCNN_E_ARG, "rect [%u,%u)x[%u,%u) outside %ux%u", x0, x1, y0, y1, dw, dh);
     if (dh > (1u << 20) || h > (1u << 20) || dw > 0x7fffffu || (y1 - y0) > 65535u * 16u)
         return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
-    if (x0 == 0 && x1 == dw && in_stride == w && out_stride == dw) return y_path_range(c, d_in, w, h, dw, dh, filter, y0, y1, d_out);
+    if (x0 == 0 && x1 == dw && whole_plane && in_x0 == 0 && in_y0 == 0 && in_stride == w && out_stride == dw)
+        return y_path_range(c, d_in, w, h, dw, dh, filter, y0, y1, d_out);
     const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
     const unsigned Ww = std::min(dw, cbx + 4) - (cax >= 4 ? cax - 4 : 0);
     const size_t row_bytes = (size_t)C2N * Ww * sizeof(float);
     const bool no_planes = c.mode == SRCNN_MODE_FAST_F16;      // the fused kernel has no layer-2 planes
     if (no_planes || row_bytes * ((size_t)(y1 - y0) + 4) <= G.ws_budget.load())
-        return y_path_rect_rows(c, d_in, in_stride, w, h, dw, dh, filter, x0, x1, y0, y1, d_out, out_stride);
+        return y_path_rect_rows(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, x0, x1, y0, y1, d_out, out_stride);
     const unsigned band = budget_band_rows(Ww);
     for (unsigned a = y0; a < y1; a += band) {
         const unsigned b = std::min(y1, a + band);
-        int rc = y_path_rect_rows(c, d_in, in_stride, w, h, dw, dh, filter, x0, x1, a, b, d_out + (size_t)(a - y0) * out_stride, out_stride);
+        int rc = y_path_rect_rows(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, x0, x1, a, b, d_out + (size_t)(a - y0) * out_stride, out_stride);
         if (rc) return rc;
     }
     return SRCNN_OK;
+}
+
+// Rows of the rect [x0,x1) x [y0,y1) that one pass of y_path_rect produces: all of them, or the band its loop above takes.
+unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1)
+{
+    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
+    const unsigned Ww = std::min(dw, cbx + 4) - (cax >= 4 ? cax - 4 : 0);
+    const size_t row_bytes = (size_t)C2N * Ww * sizeof(float);
+    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)(y1 - y0) + 4) <= G.ws_budget.load()) return y1 - y0;
+    return std::min(y1 - y0, budget_band_rows(Ww));
 }
 
 int check_y_path_args(const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const float* d_out)
@@ -1215,6 +1231,19 @@ void release_context(Ctx& cx)
 }
 
 }  // namespace
+
+// [lo,hi) of the source axis that destination indices [a,b) of the resampled axis read: the taps of the range, read off the
+// table; an axis that keeps its size is copied
+void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
+{
+    if (dst_len == src_len) { lo = a; hi = b; return; }
+    const AxisTable t = build_axis_table(filter, dst_len, src_len);
+    int l = 0x7fffffff, e = 0;
+    for (unsigned u = a; u < b; ++u) { l = std::min(l, (int)t.first[u]); e = std::max(e, (int)(t.first[u] + t.taps[u])); }
+    lo = (unsigned)l;
+    hi = std::min((unsigned)e, src_len);
+}
+
 }  // namespace srcnn
 
 using namespace srcnn;
@@ -1583,18 +1612,6 @@ int srcnn_y_upscale2x_f32_band_dev(const float* d_in, unsigned w, unsigned h, un
 // ---- one rectangle of the output (include/srcnn_amd_rect.h) --------------------------------------
 namespace {
 
-// [lo,hi) of the source axis that destination indices [a,b) of the resampled axis read: the taps of the range, read off the
-// table; an axis that keeps its size is copied
-void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
-{
-    if (dst_len == src_len) { lo = a; hi = b; return; }
-    const AxisTable t = build_axis_table(filter, dst_len, src_len);
-    int l = 0x7fffffff, e = 0;
-    for (unsigned u = a; u < b; ++u) { l = std::min(l, (int)t.first[u]); e = std::max(e, (int)(t.first[u] + t.taps[u])); }
-    lo = (unsigned)l;
-    hi = std::min((unsigned)e, src_len);
-}
-
 // what both rect entry points refuse about the geometry, in the order the header gives
 int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
 {
@@ -1651,7 +1668,7 @@ int srcnn_y_path_rect_f32_dev(const float* d_in, size_t in_pitch, unsigned w, un
     if ((rc = check_in_out_overlap(&in, 1, &out, 1))) return rc;
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
-    return y_path_rect(sc.c, d_in, in.pitch / sizeof(float), w, h, dw, dh, filter, x0, y0, x0 + rw, y0 + rh, d_out, out.pitch / sizeof(float));
+    return y_path_rect(sc.c, d_in, in.pitch / sizeof(float), 0, 0, w, h, dw, dh, filter, x0, y0, x0 + rw, y0 + rh, d_out, out.pitch / sizeof(float));
 }
 
 // ---- per-kernel timing -------------------------------------------------------------------------

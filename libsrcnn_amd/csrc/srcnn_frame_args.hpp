@@ -1,6 +1,6 @@
 // srcnn_frame_args.hpp -- the argument half of the frame calls (srcnn_frames.cpp): what a format comes down to, and everything
-// srcnn_yuv420_upscale_dev, srcnn_yuv_upscale_dev, srcnn_yuv_packed_upscale_dev and srcnn_rgb_upscale_dev refuse before any
-// device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
+// srcnn_yuv420_upscale_dev, srcnn_yuv_upscale_dev, srcnn_yuv_packed_upscale_dev, srcnn_rgb_upscale_dev and
+// srcnn_rgb_upscale_rect_dev refuse before any device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
 // runs the pitch and end-of-plane pointer arithmetic under the CPU sanitizers.  Internal.
 #pragma once
 #include <stddef.h>
@@ -206,29 +206,68 @@ inline int check_yuv_packed_args(const YuvPackedGeom& g, unsigned w, unsigned h,
     return check_in_out_overlap(&in, 1, &out, 1);
 }
 
-// out[] has room for the planes and dst_conv; conv.lo stays NULL when the caller asks for no truncated Y' plane.
-inline int check_rgb_args(const RgbRule& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[4],
-                          const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4], void* dst_conv,
-                          size_t dst_conv_pitch, unsigned& dw, unsigned& dh, YuvPlane in[4], YuvPlane out[5], YuvPlane& conv)
+// The planes of an RGB(A) call, both sides: the w x h source image, a destination of ow x oh pixels (and dst_conv of that size),
+// then the overlap rules.  out[] has room for the planes and dst_conv; conv.lo stays NULL when the caller asks for no
+// truncated Y' plane.
+inline int describe_rgb_planes(const RgbRule& g, unsigned w, unsigned h, unsigned ow, unsigned oh, const void* const src[4],
+                               const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4], void* dst_conv,
+                               size_t dst_conv_pitch, YuvPlane in[4], YuvPlane out[5], YuvPlane& conv)
 {
     const int np = g.planar ? g.ch : 1;
-    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
-    for (int k = 0; k < np; ++k)
-        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
     int rc;
-    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
     const size_t spp = g.planar ? 1 : (size_t)g.ch;                 // samples per pixel of one plane
     for (int k = 0; k < np; ++k) {
         if ((rc = describe_plane(in[k], src[k], src_pitch ? src_pitch[k] : 0, (size_t)g.bps * spp * w, h, g.bps, "input", k))) return rc;
-        if ((rc = describe_plane(out[k], dst[k], dst_pitch ? dst_pitch[k] : 0, (size_t)g.bps * spp * dw, dh, g.bps, "output", k))) return rc;
+        if ((rc = describe_plane(out[k], dst[k], dst_pitch ? dst_pitch[k] : 0, (size_t)g.bps * spp * ow, oh, g.bps, "output", k))) return rc;
     }
     int nout = np;
     if (dst_conv) {
-        if ((rc = describe_plane(conv, dst_conv, dst_conv_pitch, (size_t)g.bps * dw, dh, g.bps, "dst_conv", 0))) return rc;
+        if ((rc = describe_plane(conv, dst_conv, dst_conv_pitch, (size_t)g.bps * ow, oh, g.bps, "dst_conv", 0))) return rc;
         out[nout++] = conv;
     }
     if ((rc = check_in_out_overlap(in, np, out, nout))) return rc;
     return check_out_out_overlap(out, nout);
+}
+
+inline int check_rgb_planes_given(const RgbRule& g, const void* const src[4], void* const dst[4])
+{
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
+    for (int k = 0; k < (g.planar ? g.ch : 1); ++k)
+        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
+    return SRCNN_OK;
+}
+
+inline int check_rgb_args(const RgbRule& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[4],
+                          const size_t src_pitch[4], void* const dst[4], const size_t dst_pitch[4], void* dst_conv,
+                          size_t dst_conv_pitch, unsigned& dw, unsigned& dh, YuvPlane in[4], YuvPlane out[5], YuvPlane& conv)
+{
+    int rc;
+    if ((rc = check_rgb_planes_given(g, src, dst))) return rc;
+    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
+    return describe_rgb_planes(g, w, h, dw, dh, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, in, out, conv);
+}
+
+// A rect [x0, x0 + rw) x [y0, y0 + rh) of a dw x dh output: not empty, inside (the sums taken in 64 bits)
+inline int check_rect_inside(unsigned dw, unsigned dh, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
+{
+    if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
+    if ((unsigned long long)x0 + rw > dw || (unsigned long long)y0 + rh > dh)
+        return fail(SRCNN_E_ARG, "rect %ux%u at (%u,%u) is not inside the %ux%u output", rw, rh, x0, y0, dw, dh);
+    return SRCNN_OK;
+}
+
+// srcnn_rgb_upscale_rect_dev: the rules of check_rgb_args, with a destination (and dst_conv) of rw x rh pixels.
+inline int check_rgb_rect_args(const RgbRule& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[4],
+                               const size_t src_pitch[4], unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* const dst[4],
+                               const size_t dst_pitch[4], void* dst_conv, size_t dst_conv_pitch, unsigned& dw, unsigned& dh,
+                               YuvPlane in[4], YuvPlane out[5], YuvPlane& conv)
+{
+    int rc;
+    if ((rc = check_rgb_planes_given(g, src, dst))) return rc;
+    if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
+    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    return describe_rgb_planes(g, w, h, rw, rh, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, in, out, conv);
 }
 
 }  // namespace srcnn

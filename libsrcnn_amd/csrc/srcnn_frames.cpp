@@ -3,6 +3,7 @@
 //   include/srcnn_amd_yuv_ex.h       srcnn_yuv_upscale_dev           planar / semi-planar, 8-16 bits, 4:2:0 / 4:2:2 / 4:4:4
 //   include/srcnn_amd_yuv_packed.h   srcnn_yuv_packed_upscale_dev    YUY2, UYVY, Y210, Y410, v210 ...
 //   include/srcnn_amd_rgb.h          srcnn_rgb_upscale_dev           RGB(A), interleaved or planar, 8-16 bits
+//   include/srcnn_amd_rgb_rect.h     srcnn_rgb_upscale_rect_dev      one rectangle of that call's output, at the rect's cost
 //
 // Every call has the same skeleton: refuse what the arguments rule out before any device lookup (srcnn_frame_args.hpp), lay
 // the float planes out in ws.planes (PlaneArena), unpack the source (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip,
@@ -13,6 +14,8 @@
 
 #include <algorithm>
 
+#include "../../include/srcnn_amd_rect.h"
+#include "../../include/srcnn_amd_rgb_rect.h"
 #include "srcnn_frame_args.hpp"
 #include "srcnn_host.hpp"
 #include "srcnn_rgb.h"
@@ -187,6 +190,111 @@ int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, un
     });
 }
 
+// [lo, hi) of a source axis that destination indices [a, b) read with `filter`, off the call's cached table (an axis that keeps
+// its size is copied): what srcnn_rgb_rect_source reports, without building a table per call
+int axis_span(Call& c, int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
+{
+    if (dst_len == src_len) { lo = a; hi = b; return SRCNN_OK; }
+    TableRef t;
+    int rc;
+    if ((rc = get_table(c, filter, dst_len, src_len, t))) return rc;
+    t->source_span(a, b, lo, hi);
+    hi = std::min(hi, src_len);
+    return SRCNN_OK;
+}
+
+// [lo, hi) of an output axis the Y path computes for the rect's [a, b): +-2 (layer 3), +-4 (layer 1), cut at the borders
+void halo_span(unsigned len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
+{
+    const unsigned ca = a >= 2 ? a - 2 : 0, cb = std::min(len, b + 2);
+    lo = ca >= 4 ? ca - 4 : 0;
+    hi = std::min(len, cb + 4);
+}
+
+// The rect [x0, x1) x [y0, y1) of what rgb_frame writes, at the cost of the rect: every step works on a window.  out[] and conv
+// are the rect's own planes (pixel (x0, y0) first).  Y' comes from the window Y path (y_path_rect) band by band, in its bands.
+//   up-scale in both axes, tables of at most 8 taps:  k_rgb_window_y over the Y path's source rectangle -> per band
+//       { y_path_rect, k_rgb_window_merge: chroma / alpha resampled from the integer source, merge, store }
+//   everything else, and SRCNN_RGB_RECT_UNFUSED=1:     the plane route over the window: unpack of the source rectangle (the
+//       union of the Y path's and the chroma taps') -> per band { y_path_rect, resample_window per chroma / alpha plane, pack }
+// Both read no sample outside the rectangle srcnn_rgb_rect_source reports, and both give the bytes of rgb_frame.
+int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
+             const YuvPlane out[4], const YuvPlane& conv, unsigned x0, unsigned y0, unsigned x1, unsigned y1)
+{
+    Workspace& ws = *c.ws;
+    const int cfilter = chroma_filter(filter);
+    const unsigned rw = x1 - x0;
+    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    int rc;
+    unsigned ha, hb, ylx, yhx, yly, yhy, clx, chx, cly, chy;
+    halo_span(dw, x0, x1, ha, hb);
+    if ((rc = axis_span(c, filter, dw, w, ha, hb, ylx, yhx))) return rc;
+    halo_span(dh, y0, y1, ha, hb);
+    if ((rc = axis_span(c, filter, dh, h, ha, hb, yly, yhy))) return rc;
+    if ((rc = axis_span(c, cfilter, dw, w, x0, x1, clx, chx))) return rc;
+    if ((rc = axis_span(c, cfilter, dh, h, y0, y1, cly, chy))) return rc;
+    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
+    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
+        src[k] = in[k].lo; spitch[k] = in[k].pitch;
+        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
+    }
+    unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
+    TraceRange tr("srcnn rgb rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, y0, y1, dw, dh);
+
+    TableRef cv, ch_;
+    bool fused = !settings().rgb_rect_unfused && dw > w && dh > h;
+    if (fused) {
+        if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
+        if ((rc = get_table(c, cfilter, dw, w, ch_))) return rc;
+        for (unsigned a = y0; a < y1 && fused; a += band)
+            fused = rgb_window_merge_fits(ch_->view(), cv->view(), x0, rw, a, std::min(y1, a + band) - a);
+    }
+    PlaneArena A;
+    if (fused) {
+        // [Y of the Y path's source rectangle] [Y' of one band]
+        const unsigned yw = yhx - ylx, yh_ = yhy - yly;
+        const size_t o_y = A.take((size_t)yw * yh_), o_band = A.take((size_t)rw * band);
+        if ((rc = ws.grow(ws.planes, A.n))) return rc;
+        float* P = ws.planes.data();
+        launch_rgb_window_y(g, src, spitch, ylx, yly, yw, yh_, P + o_y, c.s);
+        const bool whole = ylx == 0 && yly == 0 && yw == w && yh_ == h;
+        for (unsigned a = y0; a < y1; a += band) {
+            const unsigned b = std::min(y1, a + band);
+            if ((rc = y_path_rect(c, P + o_y, yw, ylx, yly, w, h, dw, dh, filter, x0, a, x1, b, P + o_band, rw, whole))) return rc;
+            launch_rgb_window_merge(g, src, spitch, w, h, P + o_band, x0, a, rw, b - a, ch_->view(), cv->view(), dst, dpitch, a - y0,
+                                    d_conv, conv.pitch, c.s);
+        }
+        HIP_TRY(hipGetLastError());
+        return SRCNN_OK;
+    }
+    // [Y Cb Cr (A) of the source rectangle] [Y' Cb' Cr' (A') of one band]
+    const unsigned ux = std::min(ylx, clx), uy = std::min(yly, cly);
+    const unsigned uw = std::max(yhx, chx) - ux, uh = std::max(yhy, chy) - uy;
+    float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
+    float* dp[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t so[4], bo[4];
+    for (int k = 0; k < g.ch; ++k) so[k] = A.take((size_t)uw * uh);
+    for (int k = 0; k < g.ch; ++k) bo[k] = A.take((size_t)rw * band);
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes.data() + so[k]; dp[k] = ws.planes.data() + bo[k]; }
+    const unsigned char* wsrc[4] = {nullptr, nullptr, nullptr, nullptr};      // the planes at the source rectangle's first sample
+    for (int k = 0; k < (g.planar ? g.ch : 1); ++k)
+        wsrc[k] = src[k] + (size_t)uy * spitch[k] + (size_t)ux * g.bps * (g.planar ? 1 : g.ch);
+    launch_rgb_unpack(g, wsrc, spitch, uw, uh, sp, c.s);
+    const bool whole = ux == 0 && uy == 0 && uw == w && uh == h;
+    for (unsigned a = y0; a < y1; a += band) {
+        const unsigned b = std::min(y1, a + band);
+        if ((rc = y_path_rect(c, sp[0], uw, ux, uy, w, h, dw, dh, filter, x0, a, x1, b, dp[0], rw, whole))) return rc;
+        for (int k = 1; k < g.ch; ++k)
+            if ((rc = resample_window(c, sp[k], uw, ux, uy, w, h, dw, dh, cfilter, x0, x1, a, b, dp[k]))) return rc;
+        launch_rgb_pack(g, dp, rw, b - a, dst, dpitch, a - y0, d_conv, conv.pitch, c.s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 }  // namespace
 }  // namespace srcnn
 
@@ -316,6 +424,46 @@ int srcnn_rgb_upscale_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned h, f
     if (sc.rc) return sc.rc;
     TraceRange tr("srcnn rgb %ux%u -> %ux%u", w, h, dw, dh);
     return rgb_frame(sc.c, g, w, h, dw, dh, filter, in, out, conv);
+}
+
+// ---- one rectangle of an RGB(A) image (include/srcnn_amd_rgb_rect.h) ----
+int srcnn_rgb_rect_abi_version(void) { return SRCNN_AMD_RGB_RECT_VERSION; }
+
+int srcnn_rgb_rect_source(unsigned w, unsigned h, float multiply, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh,
+                          unsigned* sx0, unsigned* sy0, unsigned* sw, unsigned* sh)
+{
+    unsigned dw = 0, dh = 0, yx = 0, yy = 0, yw = 0, yh = 0, clx, chx, cly, chy;
+    int rc;
+    if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
+    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    if ((rc = srcnn_y_path_rect_source(w, h, dw, dh, filter, x0, y0, rw, rh, &yx, &yy, &yw, &yh))) return rc;
+    const int cfilter = chroma_filter(filter);
+    axis_source_span(cfilter, dw, w, x0, x0 + rw, clx, chx);
+    axis_source_span(cfilter, dh, h, y0, y0 + rh, cly, chy);
+    const unsigned lx = std::min(yx, clx), ly = std::min(yy, cly);
+    if (sx0) *sx0 = lx;
+    if (sy0) *sy0 = ly;
+    if (sw) *sw = std::max(yx + yw, chx) - lx;
+    if (sh) *sh = std::max(yy + yh, chy) - ly;
+    return SRCNN_OK;
+}
+
+int srcnn_rgb_upscale_rect_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                               const void* const src[4], const size_t src_pitch[4], unsigned x0, unsigned y0, unsigned rw,
+                               unsigned rh, void* const dst[4], const size_t dst_pitch[4], void* dst_conv, size_t dst_conv_pitch,
+                               void* stream)
+{
+    RgbRule g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[4], out[5], conv;
+    int rc;
+    if ((rc = rgb_rule_from_format(fmt, g))) return rc;
+    if ((rc = check_rgb_rect_args(g, w, h, multiply, filter, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, dst_conv, dst_conv_pitch,
+                                  dw, dh, in, out, conv))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    return rgb_rect(sc.c, g, w, h, dw, dh, filter, in, out, conv, x0, y0, x0 + rw, y0 + rh);
 }
 
 }  // extern "C"

@@ -311,9 +311,19 @@ int y_path_range(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw
                  unsigned r0, unsigned r1, float* d_out);
 int y_path_frame(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, float* d_out);
 // Output samples [x0,x1) x [y0,y1) of the (dw x dh) result only, at the cost of a window around them.  in_stride / out_stride
-// are in floats; d_out is where sample (x0, y0) goes.
-int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
-                unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride);
+// are in floats; d_out is where sample (x0, y0) goes.  d_in begins at sample (in_x0, in_y0) of the w x h plane and holds at least
+// the rect's source rectangle; whole_plane: it holds all h rows of the plane.
+int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned w, unsigned h, unsigned dw,
+                unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride,
+                bool whole_plane = true);
+// rows of that rect one pass produces: all of them, or the band y_path_rect cuts it into under the workspace budget
+unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1);
+// Columns [c0,c1) x rows [r0,r1) of the resampled (dw x dh) plane, tight, at the cost of that window, with the bits of
+// resample_rows_range; d_in (in_stride floats per row) begins at sample (in_x0, in_y0) of the sw x sh source plane.
+int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned sw, unsigned sh,
+                    unsigned dw, unsigned dh, int filter, unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst);
+// [lo,hi) of the source axis that destination indices [a,b) read (the taps, off a table built on the host; a kept size: [a,b))
+void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi);
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);
 // rows of layer-2 scratch one band may hold under the workspace budget (>= 16), for a dw-wide output

@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "srcnn_frame_rules.h"
+#include "srcnn_kernels.h"
 
 namespace srcnn {
 
@@ -17,5 +18,21 @@ void launch_rgb_unpack(const RgbRule& f, const unsigned char* const src[4], cons
 // sample of f.bps bytes per pixel.
 void launch_rgb_pack(const RgbRule& f, const float* const in[4], unsigned w, unsigned rows, unsigned char* const dst[4],
                      const size_t pitch[4], unsigned row0, unsigned char* conv, size_t conv_pitch, hipStream_t s);
+
+// ---- the window forms behind the rect call (srcnn_rgb_window.hip; include/srcnn_amd_rgb_rect.h) ----
+// Samples [sx0, sx0 + sw) x [sy0, sy0 + sh) of the pitched integer plane(s) src (the WHOLE image) -> a tight sw x sh float Y
+// window, with the Y line of launch_rgb_unpack.  No byte outside that rectangle is read.
+void launch_rgb_window_y(const RgbRule& f, const unsigned char* const src[4], const size_t pitch[4], unsigned sx0, unsigned sy0,
+                         unsigned sw, unsigned sh, float* y, hipStream_t s);
+// Whether launch_rgb_window_merge serves output columns [x0, x0 + rw) and rows [gy0, gy0 + rows): the tables have host
+// copies and at most 8 taps, and the source patch of every 64 x 16 tile fits the kernel's LDS.
+bool rgb_window_merge_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned x0, unsigned rw, unsigned gy0, unsigned rows);
+// One band of the rect: Cb', Cr' (and A') of output columns [x0, x0 + rw) and rows [gy0, gy0 + rows) resampled from the whole
+// w x h integer source with the tables th (columns) and tv (rows), an up-scale in both axes, merged with yband (tight, rw floats
+// per row) as launch_rgb_pack merges, into rows [row0, row0 + rows) of dst (whose first pixel is the rect's) and of conv.
+void launch_rgb_window_merge(const RgbRule& f, const unsigned char* const src[4], const size_t spitch[4], unsigned w, unsigned h,
+                             const float* yband, unsigned x0, unsigned gy0, unsigned rw, unsigned rows,
+                             const DevAxisTable& th, const DevAxisTable& tv, unsigned char* const dst[4], const size_t dpitch[4],
+                             unsigned row0, unsigned char* conv, size_t conv_pitch, hipStream_t s);
 
 }  // namespace srcnn
