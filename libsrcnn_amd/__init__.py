@@ -59,7 +59,9 @@ YUV_PACKED_SYMBOLS = ["srcnn_yuv_packed_abi_version", "srcnn_yuv_packed_row_byte
 RECT_SYMBOLS = ["srcnn_rect_abi_version", "srcnn_y_path_rect_source", "srcnn_y_path_rect_f32_dev"]
 # one rectangle of an RGB(A) image (include/srcnn_amd_rgb_rect.h, listed in include/srcnn_amd_rgb_rect.abi; its own version)
 RGB_RECT_SYMBOLS = ["srcnn_rgb_rect_abi_version", "srcnn_rgb_rect_source", "srcnn_rgb_upscale_rect_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
+# one rectangle of a planar / semi-planar YUV frame (include/srcnn_amd_yuv_rect.h, listed in include/srcnn_amd_yuv_rect.abi; its own version)
+YUV_RECT_SYMBOLS = ["srcnn_yuv_rect_abi_version", "srcnn_yuv_rect_source", "srcnn_yuv_upscale_rect_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -162,9 +164,13 @@ def lib():
             "srcnn_rgb_rect_source": (i, [u, u, f, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
             "srcnn_rgb_upscale_rect_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), u, u, u, u,
                                                C.POINTER(vp), C.POINTER(sz), vp, sz, vp]),
+            "srcnn_yuv_rect_abi_version": (i, []),
+            "srcnn_yuv_rect_source": (i, [C.POINTER(YuvFormat), u, u, f, i, u, u, u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
+            "srcnn_yuv_upscale_rect_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), u, u, u, u,
+                                               C.POINTER(vp), C.POINTER(sz), vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -641,6 +647,62 @@ def yuv_upscale(planes, layout="planar", chroma="420", depth=8, msb_aligned=Fals
     dout = [DeviceBuffer(max(1, int(np.prod(s)) * bps)) for s in shapes]
     pad = [None] * (3 - len(ins))
     yuv_upscale_dev(fmt, w, h, multiply, filt, din + pad, None, dout + pad, None, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    return tuple(b.to_numpy(dt, s) for b, s in zip(dout, shapes))
+
+
+def yuv_rect_source(fmt, w, h, multiply, filt, x0, y0, rw, rh, plane):
+    """(sx0, sy0, sw, sh): the rectangle of plane `plane` (0..2) of the w x h source frame, in that plane's own sample
+    coordinates (a UV plane: one column per pair), that output rect [x0, x0 + rw) x [y0, y0 + rh) of
+    yuv_upscale_dev(fmt, ..., multiply, filt) depends on (srcnn_yuv_rect_source; no device)."""
+    r = [C.c_uint(0) for _ in range(4)]
+    check(lib().srcnn_yuv_rect_source(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                      int(x0), int(y0), int(rw), int(rh), int(plane), *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+def yuv_upscale_rect_dev(fmt, w, h, multiply, filt, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, stream=None):
+    """srcnn_yuv_upscale_rect_dev on device memory, as given: the arguments of yuv_upscale_dev with the rect (x0, y0, rw, rh) in
+    luma output coordinates; src is the whole frame, dst the planes of an rw x rh frame (or the addresses of luma sample
+    (x0, y0) and of the chroma sample that covers it inside a full-size frame, with that frame's pitches).  Plane arguments as
+    for yuv_upscale_dev: a DeviceBuffer, an address, or (DeviceBuffer, byte offset).  Asynchronous on `stream`; raises
+    SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    s = (vp * 3)(*[_addr(p) for p in src]) if src is not None else None
+    d = (vp * 3)(*[_addr(p) for p in dst]) if dst is not None else None
+    sp = (sz * 3)(*src_pitch) if src_pitch is not None else None
+    dp = (sz * 3)(*dst_pitch) if dst_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_yuv_upscale_rect_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)),
+                                           int(filt), s, sp, int(x0), int(y0), int(rw), int(rh), d, dp, handle))
+
+
+def yuv_upscale_rect(planes, rect, layout="planar", chroma="420", depth=8, msb_aligned=False, multiply=2.0, filt=SRCNNF_Bicubic,
+                     stream=None):
+    """Rect = (x0, y0, rw, rh) (luma output coordinates) of yuv_upscale(planes, ...) through srcnn_yuv_upscale_rect_dev: numpy
+    planes of the whole frame in, the planes of the rw x rh rect out (the chroma samples that cover it), shaped as
+    yuv_upscale shapes the planes of an rw x rh frame."""
+    fmt = yuv_format(layout, chroma, depth, msb_aligned)
+    dt = np.uint8 if depth == 8 else np.uint16
+    y = np.ascontiguousarray(planes[0], dt)
+    h, w = y.shape
+    x0, y0, rw, rh = (int(v) for v in rect)
+    n = 2 if fmt.layout == YUV_SEMIPLANAR else 3
+    src_sizes = [yuv_plane_size(fmt, w, h, k) for k in range(n)]
+    bps = np.dtype(dt).itemsize
+    ins = [y] + [np.ascontiguousarray(p, dt).reshape(r, rb // bps) for p, (_c, r, rb) in zip(planes[1:], src_sizes[1:])]
+    assert len(ins) == n, "%d planes given, the format has %d" % (len(ins), n)
+    din = [DeviceBuffer.from_numpy(p) for p in ins]
+    pad = [None] * (3 - n)
+    if rw <= 0 or rh <= 0:
+        shapes, dout = [], [DeviceBuffer(1) for _ in range(n)]        # (for the library to refuse)
+    else:
+        shapes = [(r, rb // bps) for (_c, r, rb) in (yuv_plane_size(fmt, rw, rh, k) for k in range(n))]
+        dout = [DeviceBuffer(max(1, int(np.prod(s)) * bps)) for s in shapes]
+    yuv_upscale_rect_dev(fmt, w, h, multiply, filt, din + pad, None, x0, y0, rw, rh, dout + pad, None, stream)
     if isinstance(stream, Stream):
         stream.sync()
     else:

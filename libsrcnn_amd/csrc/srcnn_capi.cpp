@@ -28,6 +28,7 @@
 #include "../../include/srcnn_amd_rect.h"
 #include "srcnn_frame_args.hpp"
 #include "srcnn_host.hpp"
+#include "srcnn_rect_source.hpp"
 #include "srcnn_window.h"
 
 namespace srcnn {
@@ -1232,18 +1233,6 @@ void release_context(Ctx& cx)
 
 }  // namespace
 
-// [lo,hi) of the source axis that destination indices [a,b) of the resampled axis read: the taps of the range, read off the
-// table; an axis that keeps its size is copied
-void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
-{
-    if (dst_len == src_len) { lo = a; hi = b; return; }
-    const AxisTable t = build_axis_table(filter, dst_len, src_len);
-    int l = 0x7fffffff, e = 0;
-    for (unsigned u = a; u < b; ++u) { l = std::min(l, (int)t.first[u]); e = std::max(e, (int)(t.first[u] + t.taps[u])); }
-    lo = (unsigned)l;
-    hi = std::min((unsigned)e, src_len);
-}
-
 }  // namespace srcnn
 
 using namespace srcnn;
@@ -1640,14 +1629,8 @@ int srcnn_y_path_rect_source(unsigned w, unsigned h, unsigned dw, unsigned dh, i
     int rc;
     if ((rc = check_rect_geometry(w, h, dw, dh, filter, x0, y0, rw, rh))) return rc;
     if ((rc = check_rect_limits(w, h, dw, dh, rh))) return rc;
-    const unsigned x1 = x0 + rw, y1 = y0 + rh;
-    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
-    const unsigned uax = cax >= 4 ? cax - 4 : 0, ubx = std::min(dw, cbx + 4);
-    const unsigned cay = y0 >= 2 ? y0 - 2 : 0, cby = std::min(dh, y1 + 2);
-    const unsigned uay = cay >= 4 ? cay - 4 : 0, uby = std::min(dh, cby + 4);
     unsigned lx, hx, ly, hy;
-    axis_source_span(filter, dw, w, uax, ubx, lx, hx);
-    axis_source_span(filter, dh, h, uay, uby, ly, hy);
+    y_path_rect_source_span(w, h, dw, dh, filter, x0, y0, x0 + rw, y0 + rh, lx, hx, ly, hy);
     if (sx0) *sx0 = lx;
     if (sy0) *sy0 = ly;
     if (sw) *sw = hx - lx;

@@ -1,6 +1,6 @@
 // srcnn_frame_args.hpp -- the argument half of the frame calls (srcnn_frames.cpp): what a format comes down to, and everything
-// srcnn_yuv420_upscale_dev, srcnn_yuv_upscale_dev, srcnn_yuv_packed_upscale_dev, srcnn_rgb_upscale_dev and
-// srcnn_rgb_upscale_rect_dev refuse before any device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
+// srcnn_yuv420_upscale_dev, srcnn_yuv_upscale_dev, srcnn_yuv_packed_upscale_dev, srcnn_rgb_upscale_dev,
+// srcnn_rgb_upscale_rect_dev and srcnn_yuv_upscale_rect_dev refuse before any device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
 // runs the pitch and end-of-plane pointer arithmetic under the CPU sanitizers.  Internal.
 #pragma once
 #include <stddef.h>
@@ -268,6 +268,52 @@ inline int check_rgb_rect_args(const RgbRule& g, unsigned w, unsigned h, float m
     if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
     if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
     return describe_rgb_planes(g, w, h, rw, rh, src, src_pitch, dst, dst_pitch, dst_conv, dst_conv_pitch, in, out, conv);
+}
+
+// The chroma samples that cover luma rect [x0, x1) x [y0, y1): [cx0, cx1) x [cy0, cy1) on the chroma grid.  x0 (y0) is even
+// where the format subsamples that axis, so these are the chroma planes of an (x1 - x0) x (y1 - y0) frame.
+struct YuvChromaRect {
+    unsigned cx0, cy0, cx1, cy1;
+    YuvChromaRect(const YuvGeom& g, unsigned x0, unsigned y0, unsigned x1, unsigned y1)
+        : cx0(x0 >> g.sx), cy0(y0 >> g.sy), cx1(g.ccols(x1)), cy1(g.crows(y1)) {}
+};
+
+// A rect origin the chroma grid cannot express: odd x0 under horizontal subsampling, odd y0 under vertical
+inline int check_yuv_rect_origin(const YuvGeom& g, unsigned x0, unsigned y0)
+{
+    if ((g.sx && (x0 & 1)) || (g.sy && (y0 & 1)))
+        return fail(SRCNN_E_ARG, "rect origin (%u,%u) must be even where the format subsamples chroma (columns: %s, rows: %s)", x0, y0,
+                    g.sx ? "yes" : "no", g.sy ? "yes" : "no");
+    return SRCNN_OK;
+}
+
+// srcnn_yuv_upscale_rect_dev: the rules of check_yuv_args with the WHOLE w x h frame as the source and the planes of an rw x rh
+// frame as the destination, the rect's own rules between the scale and the planes, and -- unlike the whole-frame calls --
+// destination planes that overlap each other refused (a rect is repainted inside a shared surface: a slip shows here first).
+inline int check_yuv_rect_args(const YuvGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[3],
+                               const size_t src_pitch[3], unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* const dst[3],
+                               const size_t dst_pitch[3], unsigned& dw, unsigned& dh, YuvPlane in[3], YuvPlane out[3])
+{
+    const int np = g.semi ? 2 : 3;
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL plane array");
+    for (int k = 0; k < np; ++k)
+        if (!src[k] || !dst[k]) return fail(SRCNN_E_ARG, "NULL plane %d", k);
+    if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
+    int rc;
+    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    if ((rc = check_yuv_rect_origin(g, x0, y0))) return rc;
+    for (int side = 0; side < 2; ++side) {
+        const unsigned pw = side ? rw : w, ph = side ? rh : h, pcw = g.ccols(pw), pch = g.crows(ph);
+        const size_t* pitch = side ? dst_pitch : src_pitch;
+        for (int k = 0; k < np; ++k) {
+            const size_t row_bytes = (size_t)g.bps * (k == 0 ? pw : (g.semi ? 2 * (size_t)pcw : pcw));
+            if ((rc = describe_plane((side ? out : in)[k], side ? dst[k] : src[k], pitch ? pitch[k] : 0, row_bytes, k == 0 ? ph : pch,
+                                     g.bps, side ? "output" : "input", k))) return rc;
+        }
+    }
+    if ((rc = check_in_out_overlap(in, np, out, np))) return rc;
+    return check_out_out_overlap(out, np);
 }
 
 }  // namespace srcnn

@@ -4,6 +4,7 @@
 //   include/srcnn_amd_yuv_packed.h   srcnn_yuv_packed_upscale_dev    YUY2, UYVY, Y210, Y410, v210 ...
 //   include/srcnn_amd_rgb.h          srcnn_rgb_upscale_dev           RGB(A), interleaved or planar, 8-16 bits
 //   include/srcnn_amd_rgb_rect.h     srcnn_rgb_upscale_rect_dev      one rectangle of that call's output, at the rect's cost
+//   include/srcnn_amd_yuv_rect.h     srcnn_yuv_upscale_rect_dev      one rectangle of srcnn_yuv_upscale_dev's output, likewise
 //
 // Every call has the same skeleton: refuse what the arguments rule out before any device lookup (srcnn_frame_args.hpp), lay
 // the float planes out in ws.planes (PlaneArena), unpack the source (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip,
@@ -16,8 +17,10 @@
 
 #include "../../include/srcnn_amd_rect.h"
 #include "../../include/srcnn_amd_rgb_rect.h"
+#include "../../include/srcnn_amd_yuv_rect.h"
 #include "srcnn_frame_args.hpp"
 #include "srcnn_host.hpp"
+#include "srcnn_rect_source.hpp"
 #include "srcnn_rgb.h"
 #include "srcnn_yuv.h"
 
@@ -31,9 +34,6 @@ struct PlaneArena {
     size_t n = 0;           // floats needed so far
     size_t take(size_t k) { const size_t o = (n + 63) & ~(size_t)63; n = o + k; return o; }
 };
-
-// chroma and alpha planes: nearest stays nearest, everything else is bilinear (as J.cfilter of srcnn_process_u8)
-int chroma_filter(int filter) { return filter == SRCNN_FILTER_NEAREST ? SRCNN_FILTER_NEAREST : SRCNN_FILTER_BILINEAR; }
 
 // Rows of Y' one pass of the Y path produces: the whole frame when its layer-2 planes fit the workspace cap (y_path_range's
 // test), else budget_band_rows.
@@ -295,6 +295,81 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
     return SRCNN_OK;
 }
 
+// The luma rect [x0, x1) x [y0, y1) and the chroma samples that cover it (cr) of what yuv_frame writes, at the cost of the rect.
+// out[] are the rect's own planes (luma sample (x0, y0) and chroma sample (cr.cx0, cr.cy0) first).
+//   Y':      unpack of the Y path's source rectangle -> per band { y_path_rect, pack }
+//   chroma:  once for the rect, not per band.  Up-scale in both axes of the CHROMA grid, tables of at most 8 taps:
+//            k_yuv_window_chroma from the integer source.  Everything else, and SRCNN_YUV_RECT_UNFUSED=1: the plane route over the
+//            window: unpack of the chroma source rectangle -> resample_window per plane -> pack.
+// Both read no sample outside the rectangles srcnn_yuv_rect_source reports, and both give the bytes of yuv_frame.
+int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
+             const YuvPlane out[3], unsigned x0, unsigned y0, unsigned x1, unsigned y1)
+{
+    Workspace& ws = *c.ws;
+    const int cfilter = chroma_filter(filter);
+    const YuvChromaRect cr(g, x0, y0, x1, y1);
+    const unsigned rw = x1 - x0, crw = cr.cx1 - cr.cx0, crh = cr.cy1 - cr.cy0;
+    const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
+    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    const unsigned spp = g.semi ? 2 : 1;                 // samples per column of a chroma plane
+    const int ncp = g.semi ? 1 : 2;                      // chroma planes in memory
+    int rc;
+    unsigned ha, hb, ylx, yhx, yly, yhy, clx, chx, cly, chy;
+    halo_span(dw, x0, x1, ha, hb);
+    if ((rc = axis_span(c, filter, dw, w, ha, hb, ylx, yhx))) return rc;
+    halo_span(dh, y0, y1, ha, hb);
+    if ((rc = axis_span(c, filter, dh, h, ha, hb, yly, yhy))) return rc;
+    if ((rc = axis_span(c, cfilter, dcw, cw, cr.cx0, cr.cx1, clx, chx))) return rc;
+    if ((rc = axis_span(c, cfilter, dch, ch, cr.cy0, cr.cy1, cly, chy))) return rc;
+    const unsigned yw = yhx - ylx, yh_ = yhy - yly, cuw = chx - clx, cuh = chy - cly;
+    TraceRange tr("srcnn yuv rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, y0, y1, dw, dh);
+
+    TableRef cv, ch_;
+    bool fused = !settings().yuv_rect_unfused && dcw > cw && dch > ch;
+    if (fused) {
+        if ((rc = get_table(c, cfilter, dch, ch, cv))) return rc;
+        if ((rc = get_table(c, cfilter, dcw, cw, ch_))) return rc;
+        fused = yuv_window_chroma_fits(ch_->view(), cv->view(), cr.cx0, crw, cr.cy0, crh);
+    }
+    // [Y of the Y path's source rectangle] [Y' of one band] and, on the plane route, [U V of the chroma source rectangle] [U' V']
+    PlaneArena A;
+    const size_t o_y = A.take((size_t)yw * yh_), o_band = A.take((size_t)rw * band);
+    size_t o_c[2] = {0, 0}, o_dc[2] = {0, 0};
+    if (!fused) {
+        for (int k = 0; k < 2; ++k) o_c[k] = A.take((size_t)cuw * cuh);
+        for (int k = 0; k < 2; ++k) o_dc[k] = A.take((size_t)crw * crh);
+    }
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    float* P = ws.planes.data();
+    const Yuv16Rule* rule = g.bps == 2 ? &g.rule : nullptr;
+    unsigned char* dst[3];
+    for (int k = 0; k < 3; ++k) dst[k] = const_cast<unsigned char*>(out[k].lo);
+
+    if (fused) {
+        const unsigned char* csrc[2] = {in[1].lo, in[2].lo};
+        const size_t cspitch[2] = {in[1].pitch, in[2].pitch}, cdpitch[2] = {out[1].pitch, out[2].pitch};
+        launch_yuv_window_chroma(csrc, cspitch, cw, ch, g.semi, rule, cr.cx0, cr.cy0, crw, crh, ch_->view(), cv->view(), dst + 1, cdpitch, c.s);
+    } else {
+        for (int k = 0; k < ncp; ++k)                    // the planes at the chroma source rectangle's first sample
+            launch_plane_unpack(in[1 + k].lo + (size_t)cly * in[1 + k].pitch + (size_t)clx * g.bps * spp, in[1 + k].pitch, cuw, cuh, g.semi,
+                                rule, false, P + o_c[k], g.semi ? P + o_c[1] : nullptr, c.s);
+        for (int k = 0; k < 2; ++k)
+            if ((rc = resample_window(c, P + o_c[k], cuw, clx, cly, cw, ch, dcw, dch, cfilter, cr.cx0, cr.cx1, cr.cy0, cr.cy1, P + o_dc[k]))) return rc;
+        for (int k = 0; k < ncp; ++k)
+            launch_plane_pack(P + o_dc[k], g.semi ? P + o_dc[1] : nullptr, crw, crh, true, rule, dst[1 + k], out[1 + k].pitch, 0, c.s);
+    }
+
+    launch_plane_unpack(in[0].lo + (size_t)yly * in[0].pitch + (size_t)ylx * g.bps, in[0].pitch, yw, yh_, false, rule, true, P + o_y, nullptr, c.s);
+    const bool whole = ylx == 0 && yly == 0 && yw == w && yh_ == h;
+    for (unsigned a = y0; a < y1; a += band) {
+        const unsigned b = std::min(y1, a + band);
+        if ((rc = y_path_rect(c, P + o_y, yw, ylx, yly, w, h, dw, dh, filter, x0, a, x1, b, P + o_band, rw, whole))) return rc;
+        launch_plane_pack(P + o_band, nullptr, rw, b - a, false, rule, dst[0], out[0].pitch, a - y0, c.s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 }  // namespace
 }  // namespace srcnn
 
@@ -464,6 +539,30 @@ int srcnn_rgb_upscale_rect_dev(const srcnn_rgb_format* fmt, unsigned w, unsigned
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
     return rgb_rect(sc.c, g, w, h, dw, dh, filter, in, out, conv, x0, y0, x0 + rw, y0 + rh);
+}
+
+// ---- one rectangle of a planar / semi-planar YUV frame (include/srcnn_amd_yuv_rect.h) ----
+int srcnn_yuv_rect_abi_version(void) { return SRCNN_AMD_YUV_RECT_VERSION; }
+
+int srcnn_yuv_rect_source(const srcnn_yuv_format* fmt, unsigned w, unsigned h, float multiply, int filter, unsigned x0, unsigned y0,
+                          unsigned rw, unsigned rh, int plane, unsigned* sx0, unsigned* sy0, unsigned* sw, unsigned* sh)
+{
+    return yuv_rect_source(fmt, w, h, multiply, filter, x0, y0, rw, rh, plane, sx0, sy0, sw, sh);
+}
+
+int srcnn_yuv_upscale_rect_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned h, float multiply, int filter,
+                               const void* const src[3], const size_t src_pitch[3], unsigned x0, unsigned y0, unsigned rw,
+                               unsigned rh, void* const dst[3], const size_t dst_pitch[3], void* stream)
+{
+    YuvGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in[3], out[3];
+    int rc;
+    if ((rc = yuv_geom_from_format(fmt, g))) return rc;
+    if ((rc = check_yuv_rect_args(g, w, h, multiply, filter, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    return yuv_rect(sc.c, g, w, h, dw, dh, filter, in, out, x0, y0, x0 + rw, y0 + rh);
 }
 
 }  // extern "C"

@@ -322,8 +322,7 @@ unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned
 // resample_rows_range; d_in (in_stride floats per row) begins at sample (in_x0, in_y0) of the sw x sh source plane.
 int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned sw, unsigned sh,
                     unsigned dw, unsigned dh, int filter, unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst);
-// [lo,hi) of the source axis that destination indices [a,b) read (the taps, off a table built on the host; a kept size: [a,b))
-void axis_source_span(int filter, unsigned dst_len, unsigned src_len, unsigned a, unsigned b, unsigned& lo, unsigned& hi);
+// (axis_source_span, the source span of a range of an axis without a device, is srcnn_rect_source.hpp)
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);
 // rows of layer-2 scratch one band may hold under the workspace budget (>= 16), for a dw-wide output

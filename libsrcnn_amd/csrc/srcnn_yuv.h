@@ -1,12 +1,13 @@
 // srcnn_yuv.h -- internal interface of the YUV conversion kernels: planar and semi-planar frames of every supported depth
-// (srcnn_yuv_planes.hip) and packed frames (srcnn_yuv_packed.hip).  The rules the launchers take are srcnn_frame_rules.h; the host
+// (srcnn_yuv_planes.hip), their chroma over a window (srcnn_yuv_window.hip) and packed frames (srcnn_yuv_packed.hip).  The rules the launchers take are srcnn_frame_rules.h; the host
 // side is srcnn_frames.cpp.  Not installed; the public surface is include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h and
-// srcnn_amd_yuv_packed.h.
+// srcnn_amd_yuv_packed.h; the rect call is include/srcnn_amd_yuv_rect.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "srcnn_frame_rules.h"
+#include "srcnn_kernels.h"
 
 namespace srcnn {
 
@@ -21,6 +22,18 @@ void launch_plane_unpack(const unsigned char* src, size_t pitch, unsigned w, uns
 // truncation (chroma).  s1 != NULL: `w` pairs (s0[i], s1[i]) interleaved per row, saturated.
 void launch_plane_pack(const float* s0, const float* s1, unsigned w, unsigned rows, bool sat, const Yuv16Rule* f,
                        unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s);
+
+// ---- the window form behind the rect call (srcnn_yuv_window.hip; include/srcnn_amd_yuv_rect.h) ----
+// Whether launch_yuv_window_chroma serves chroma output columns [cx0, cx0 + cols) and rows [cy0, cy0 + rows): the tables have
+// host copies and at most 8 taps, and the source patch of every 64 x 16 tile fits the kernel's LDS.
+bool yuv_window_chroma_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned cx0, unsigned cols, unsigned cy0, unsigned rows);
+// U' and V' of chroma output columns [cx0, cx0 + cols) and rows [cy0, cy0 + rows) resampled from the WHOLE cw x ch integer
+// chroma plane(s) src with the tables th (columns) and tv (rows), an up-scale in both axes, saturated and written as
+// launch_plane_pack writes chroma, into dst, whose first sample is the rect's.  semi: src[0] / dst[0] hold (U, V) pairs, else
+// src[0] / dst[0] are U and src[1] / dst[1] V.  f as for launch_plane_unpack.  No source byte outside the taps' span is read.
+void launch_yuv_window_chroma(const unsigned char* const src[2], const size_t spitch[2], unsigned cw, unsigned ch, bool semi,
+                              const Yuv16Rule* f, unsigned cx0, unsigned cy0, unsigned cols, unsigned rows, const DevAxisTable& th,
+                              const DevAxisTable& tv, unsigned char* const dst[2], const size_t dpitch[2], hipStream_t s);
 
 // ---- packed frames: one plane that interleaves Y, U, V (and A) (srcnn_yuv_packed.hip) ----
 // Packed rows [0, rows) of `w` pixels -> tight float planes: dy (w per row, scaled by f.down), du / dv (ceil(w/2) per row for
