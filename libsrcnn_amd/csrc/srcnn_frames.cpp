@@ -22,6 +22,7 @@
 #include "srcnn_host.hpp"
 #include "srcnn_rect_source.hpp"
 #include "srcnn_rgb.h"
+#include "srcnn_window_tile.h"
 #include "srcnn_yuv.h"
 
 namespace srcnn {
@@ -129,6 +130,20 @@ int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, un
     });
 }
 
+// The planes of an RGB(A) call as the conversion launchers take them (interleaved: plane 0 only)
+struct RgbPlanes {
+    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
+    RgbPlanes(const RgbRule& g, const YuvPlane in[4], const YuvPlane out[4])
+    {
+        for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
+            src[k] = in[k].lo; spitch[k] = in[k].pitch;
+            dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
+        }
+    }
+};
+
 // The reference's own format (8-bit interleaved R,G,B[,A], tight rows, an up-scale in both axes) goes through the fused shell
 // of srcnn_process_u8: Y' from the interleaved source (k_rs2d), then the merge with on-the-fly chroma -- no float plane of
 // source or destination size.  Everything else: unpack -> per band { Y path, chroma / alpha resample, pack }.  conv.lo == NULL:
@@ -174,18 +189,12 @@ int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, un
     for (int k = 0; k < g.ch; ++k) bo[k] = A.take((size_t)dw * band);
     if ((rc = ws.grow(ws.planes, A.n))) return rc;
     for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes.data() + so[k]; dp[k] = ws.planes.data() + bo[k]; }
-    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
-    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
-        src[k] = in[k].lo; spitch[k] = in[k].pitch;
-        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
-    }
-    launch_rgb_unpack(g, src, spitch, w, h, sp, c.s);
+    const RgbPlanes pl(g, in, out);
+    launch_rgb_unpack(g, pl.src, pl.spitch, w, h, sp, c.s);
     return for_each_y_band(c, YSource::from_plane(sp[0]), w, h, dw, dh, filter, band, dp[0], [&](unsigned a, unsigned b) {
         for (int k = 1; k < g.ch; ++k)
             if (int rk = resample_rows_range(c, sp[k], w, h, dw, dh, cfilter, a, b, dp[k])) return rk;
-        launch_rgb_pack(g, dp, dw, b - a, dst, dpitch, a, const_cast<unsigned char*>(conv.lo), conv.pitch, c.s);
+        launch_rgb_pack(g, dp, dw, b - a, pl.dst, pl.dpitch, a, const_cast<unsigned char*>(conv.lo), conv.pitch, c.s);
         return SRCNN_OK;
     });
 }
@@ -211,6 +220,48 @@ void halo_span(unsigned len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
     hi = std::min(len, cb + 4);
 }
 
+// The source rectangles of a rect, each [lx, hx) x [ly, hy): what the Y path reads of the luma plane (the halo of the luma rect,
+// then the taps of `filter`), and what the taps of `cfilter` read of a chroma / alpha plane for the chroma rect
+struct RectSource {
+    unsigned ylx, yhx, yly, yhy;
+    unsigned clx, chx, cly, chy;
+    unsigned yw() const { return yhx - ylx; }
+    unsigned yh() const { return yhy - yly; }
+};
+
+// luma: w x h -> dw x dh, rect [x0, x1) x [y0, y1); chroma: cw x ch -> dcw x dch, rect [cx0, cx1) x [cy0, cy1)
+int rect_source(Call& c, int filter, int cfilter, unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned cw, unsigned ch, unsigned dcw,
+                unsigned dch, unsigned x0, unsigned y0, unsigned x1, unsigned y1, unsigned cx0, unsigned cy0, unsigned cx1, unsigned cy1,
+                RectSource& r)
+{
+    int rc;
+    unsigned ha, hb;
+    halo_span(dw, x0, x1, ha, hb);
+    if ((rc = axis_span(c, filter, dw, w, ha, hb, r.ylx, r.yhx))) return rc;
+    halo_span(dh, y0, y1, ha, hb);
+    if ((rc = axis_span(c, filter, dh, h, ha, hb, r.yly, r.yhy))) return rc;
+    if ((rc = axis_span(c, cfilter, dcw, cw, cx0, cx1, r.clx, r.chx))) return rc;
+    if ((rc = axis_span(c, cfilter, dch, ch, cy0, cy1, r.cly, r.chy))) return rc;
+    return SRCNN_OK;
+}
+
+// Y' of the rect [x0, x1) x [y0, y1) in bands of `band` rows: the window Y path writes rows [a, b) to yband (tight, x1 - x0
+// floats per row) from ysrc, the sw x sh float window of the Y plane whose first sample is (sx, sy); then after(a, b)
+template <class After>
+int for_each_rect_band(Call& c, const float* ysrc, unsigned sx, unsigned sy, unsigned sw, unsigned sh, unsigned w, unsigned h, unsigned dw,
+                       unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1, unsigned y1, unsigned band, float* yband, After after)
+{
+    const bool whole = sx == 0 && sy == 0 && sw == w && sh == h;
+    for (unsigned a = y0; a < y1; a += band) {
+        const unsigned b = std::min(y1, a + band);
+        int rc;
+        if ((rc = y_path_rect(c, ysrc, sw, sx, sy, w, h, dw, dh, filter, x0, a, x1, b, yband, x1 - x0, whole))) return rc;
+        if ((rc = after(a, b))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+}
+
 // The rect [x0, x1) x [y0, y1) of what rgb_frame writes, at the cost of the rect: every step works on a window.  out[] and conv
 // are the rect's own planes (pixel (x0, y0) first).  Y' comes from the window Y path (y_path_rect) band by band, in its bands.
 //   up-scale in both axes, tables of at most 8 taps:  k_rgb_window_y over the Y path's source rectangle -> per band
@@ -226,20 +277,9 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
     const unsigned rw = x1 - x0;
     const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
     int rc;
-    unsigned ha, hb, ylx, yhx, yly, yhy, clx, chx, cly, chy;
-    halo_span(dw, x0, x1, ha, hb);
-    if ((rc = axis_span(c, filter, dw, w, ha, hb, ylx, yhx))) return rc;
-    halo_span(dh, y0, y1, ha, hb);
-    if ((rc = axis_span(c, filter, dh, h, ha, hb, yly, yhy))) return rc;
-    if ((rc = axis_span(c, cfilter, dw, w, x0, x1, clx, chx))) return rc;
-    if ((rc = axis_span(c, cfilter, dh, h, y0, y1, cly, chy))) return rc;
-    const unsigned char* src[4] = {nullptr, nullptr, nullptr, nullptr};
-    unsigned char* dst[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t spitch[4] = {0, 0, 0, 0}, dpitch[4] = {0, 0, 0, 0};
-    for (int k = 0; k < (g.planar ? g.ch : 1); ++k) {
-        src[k] = in[k].lo; spitch[k] = in[k].pitch;
-        dst[k] = const_cast<unsigned char*>(out[k].lo); dpitch[k] = out[k].pitch;
-    }
+    RectSource r;
+    if ((rc = rect_source(c, filter, cfilter, w, h, dw, dh, w, h, dw, dh, x0, y0, x1, y1, x0, y0, x1, y1, r))) return rc;
+    const RgbPlanes pl(g, in, out);
     unsigned char* d_conv = const_cast<unsigned char*>(conv.lo);
     TraceRange tr("srcnn rgb rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, y0, y1, dw, dh);
 
@@ -249,29 +289,25 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
         if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
         if ((rc = get_table(c, cfilter, dw, w, ch_))) return rc;
         for (unsigned a = y0; a < y1 && fused; a += band)
-            fused = rgb_window_merge_fits(ch_->view(), cv->view(), x0, rw, a, std::min(y1, a + band) - a);
+            fused = window_tile_fits(ch_->view(), cv->view(), x0, rw, a, std::min(y1, a + band) - a);
     }
     PlaneArena A;
     if (fused) {
         // [Y of the Y path's source rectangle] [Y' of one band]
-        const unsigned yw = yhx - ylx, yh_ = yhy - yly;
-        const size_t o_y = A.take((size_t)yw * yh_), o_band = A.take((size_t)rw * band);
+        const size_t o_y = A.take((size_t)r.yw() * r.yh()), o_band = A.take((size_t)rw * band);
         if ((rc = ws.grow(ws.planes, A.n))) return rc;
         float* P = ws.planes.data();
-        launch_rgb_window_y(g, src, spitch, ylx, yly, yw, yh_, P + o_y, c.s);
-        const bool whole = ylx == 0 && yly == 0 && yw == w && yh_ == h;
-        for (unsigned a = y0; a < y1; a += band) {
-            const unsigned b = std::min(y1, a + band);
-            if ((rc = y_path_rect(c, P + o_y, yw, ylx, yly, w, h, dw, dh, filter, x0, a, x1, b, P + o_band, rw, whole))) return rc;
-            launch_rgb_window_merge(g, src, spitch, w, h, P + o_band, x0, a, rw, b - a, ch_->view(), cv->view(), dst, dpitch, a - y0,
-                                    d_conv, conv.pitch, c.s);
-        }
-        HIP_TRY(hipGetLastError());
-        return SRCNN_OK;
+        launch_rgb_window_y(g, pl.src, pl.spitch, r.ylx, r.yly, r.yw(), r.yh(), P + o_y, c.s);
+        return for_each_rect_band(c, P + o_y, r.ylx, r.yly, r.yw(), r.yh(), w, h, dw, dh, filter, x0, y0, x1, y1, band, P + o_band,
+                                  [&](unsigned a, unsigned b) {
+            launch_rgb_window_merge(g, pl.src, pl.spitch, w, h, P + o_band, x0, a, rw, b - a, ch_->view(), cv->view(), pl.dst, pl.dpitch,
+                                    a - y0, d_conv, conv.pitch, c.s);
+            return SRCNN_OK;
+        });
     }
     // [Y Cb Cr (A) of the source rectangle] [Y' Cb' Cr' (A') of one band]
-    const unsigned ux = std::min(ylx, clx), uy = std::min(yly, cly);
-    const unsigned uw = std::max(yhx, chx) - ux, uh = std::max(yhy, chy) - uy;
+    const unsigned ux = std::min(r.ylx, r.clx), uy = std::min(r.yly, r.cly);
+    const unsigned uw = std::max(r.yhx, r.chx) - ux, uh = std::max(r.yhy, r.chy) - uy;
     float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
     float* dp[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t so[4], bo[4];
@@ -281,18 +317,14 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
     for (int k = 0; k < g.ch; ++k) { sp[k] = ws.planes.data() + so[k]; dp[k] = ws.planes.data() + bo[k]; }
     const unsigned char* wsrc[4] = {nullptr, nullptr, nullptr, nullptr};      // the planes at the source rectangle's first sample
     for (int k = 0; k < (g.planar ? g.ch : 1); ++k)
-        wsrc[k] = src[k] + (size_t)uy * spitch[k] + (size_t)ux * g.bps * (g.planar ? 1 : g.ch);
-    launch_rgb_unpack(g, wsrc, spitch, uw, uh, sp, c.s);
-    const bool whole = ux == 0 && uy == 0 && uw == w && uh == h;
-    for (unsigned a = y0; a < y1; a += band) {
-        const unsigned b = std::min(y1, a + band);
-        if ((rc = y_path_rect(c, sp[0], uw, ux, uy, w, h, dw, dh, filter, x0, a, x1, b, dp[0], rw, whole))) return rc;
+        wsrc[k] = pl.src[k] + (size_t)uy * pl.spitch[k] + (size_t)ux * g.bps * (g.planar ? 1 : g.ch);
+    launch_rgb_unpack(g, wsrc, pl.spitch, uw, uh, sp, c.s);
+    return for_each_rect_band(c, sp[0], ux, uy, uw, uh, w, h, dw, dh, filter, x0, y0, x1, y1, band, dp[0], [&](unsigned a, unsigned b) {
         for (int k = 1; k < g.ch; ++k)
-            if ((rc = resample_window(c, sp[k], uw, ux, uy, w, h, dw, dh, cfilter, x0, x1, a, b, dp[k]))) return rc;
-        launch_rgb_pack(g, dp, rw, b - a, dst, dpitch, a - y0, d_conv, conv.pitch, c.s);
-    }
-    HIP_TRY(hipGetLastError());
-    return SRCNN_OK;
+            if (int rk = resample_window(c, sp[k], uw, ux, uy, w, h, dw, dh, cfilter, x0, x1, a, b, dp[k])) return rk;
+        launch_rgb_pack(g, dp, rw, b - a, pl.dst, pl.dpitch, a - y0, d_conv, conv.pitch, c.s);
+        return SRCNN_OK;
+    });
 }
 
 // The luma rect [x0, x1) x [y0, y1) and the chroma samples that cover it (cr) of what yuv_frame writes, at the cost of the rect.
@@ -314,14 +346,9 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
     const unsigned spp = g.semi ? 2 : 1;                 // samples per column of a chroma plane
     const int ncp = g.semi ? 1 : 2;                      // chroma planes in memory
     int rc;
-    unsigned ha, hb, ylx, yhx, yly, yhy, clx, chx, cly, chy;
-    halo_span(dw, x0, x1, ha, hb);
-    if ((rc = axis_span(c, filter, dw, w, ha, hb, ylx, yhx))) return rc;
-    halo_span(dh, y0, y1, ha, hb);
-    if ((rc = axis_span(c, filter, dh, h, ha, hb, yly, yhy))) return rc;
-    if ((rc = axis_span(c, cfilter, dcw, cw, cr.cx0, cr.cx1, clx, chx))) return rc;
-    if ((rc = axis_span(c, cfilter, dch, ch, cr.cy0, cr.cy1, cly, chy))) return rc;
-    const unsigned yw = yhx - ylx, yh_ = yhy - yly, cuw = chx - clx, cuh = chy - cly;
+    RectSource r;
+    if ((rc = rect_source(c, filter, cfilter, w, h, dw, dh, cw, ch, dcw, dch, x0, y0, x1, y1, cr.cx0, cr.cy0, cr.cx1, cr.cy1, r))) return rc;
+    const unsigned cuw = r.chx - r.clx, cuh = r.chy - r.cly;
     TraceRange tr("srcnn yuv rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, y0, y1, dw, dh);
 
     TableRef cv, ch_;
@@ -329,11 +356,11 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
     if (fused) {
         if ((rc = get_table(c, cfilter, dch, ch, cv))) return rc;
         if ((rc = get_table(c, cfilter, dcw, cw, ch_))) return rc;
-        fused = yuv_window_chroma_fits(ch_->view(), cv->view(), cr.cx0, crw, cr.cy0, crh);
+        fused = window_tile_fits(ch_->view(), cv->view(), cr.cx0, crw, cr.cy0, crh);
     }
     // [Y of the Y path's source rectangle] [Y' of one band] and, on the plane route, [U V of the chroma source rectangle] [U' V']
     PlaneArena A;
-    const size_t o_y = A.take((size_t)yw * yh_), o_band = A.take((size_t)rw * band);
+    const size_t o_y = A.take((size_t)r.yw() * r.yh()), o_band = A.take((size_t)rw * band);
     size_t o_c[2] = {0, 0}, o_dc[2] = {0, 0};
     if (!fused) {
         for (int k = 0; k < 2; ++k) o_c[k] = A.take((size_t)cuw * cuh);
@@ -351,23 +378,21 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
         launch_yuv_window_chroma(csrc, cspitch, cw, ch, g.semi, rule, cr.cx0, cr.cy0, crw, crh, ch_->view(), cv->view(), dst + 1, cdpitch, c.s);
     } else {
         for (int k = 0; k < ncp; ++k)                    // the planes at the chroma source rectangle's first sample
-            launch_plane_unpack(in[1 + k].lo + (size_t)cly * in[1 + k].pitch + (size_t)clx * g.bps * spp, in[1 + k].pitch, cuw, cuh, g.semi,
+            launch_plane_unpack(in[1 + k].lo + (size_t)r.cly * in[1 + k].pitch + (size_t)r.clx * g.bps * spp, in[1 + k].pitch, cuw, cuh, g.semi,
                                 rule, false, P + o_c[k], g.semi ? P + o_c[1] : nullptr, c.s);
         for (int k = 0; k < 2; ++k)
-            if ((rc = resample_window(c, P + o_c[k], cuw, clx, cly, cw, ch, dcw, dch, cfilter, cr.cx0, cr.cx1, cr.cy0, cr.cy1, P + o_dc[k]))) return rc;
+            if ((rc = resample_window(c, P + o_c[k], cuw, r.clx, r.cly, cw, ch, dcw, dch, cfilter, cr.cx0, cr.cx1, cr.cy0, cr.cy1, P + o_dc[k]))) return rc;
         for (int k = 0; k < ncp; ++k)
             launch_plane_pack(P + o_dc[k], g.semi ? P + o_dc[1] : nullptr, crw, crh, true, rule, dst[1 + k], out[1 + k].pitch, 0, c.s);
     }
 
-    launch_plane_unpack(in[0].lo + (size_t)yly * in[0].pitch + (size_t)ylx * g.bps, in[0].pitch, yw, yh_, false, rule, true, P + o_y, nullptr, c.s);
-    const bool whole = ylx == 0 && yly == 0 && yw == w && yh_ == h;
-    for (unsigned a = y0; a < y1; a += band) {
-        const unsigned b = std::min(y1, a + band);
-        if ((rc = y_path_rect(c, P + o_y, yw, ylx, yly, w, h, dw, dh, filter, x0, a, x1, b, P + o_band, rw, whole))) return rc;
+    launch_plane_unpack(in[0].lo + (size_t)r.yly * in[0].pitch + (size_t)r.ylx * g.bps, in[0].pitch, r.yw(), r.yh(), false, rule, true, P + o_y,
+                        nullptr, c.s);
+    return for_each_rect_band(c, P + o_y, r.ylx, r.yly, r.yw(), r.yh(), w, h, dw, dh, filter, x0, y0, x1, y1, band, P + o_band,
+                              [&](unsigned a, unsigned b) {
         launch_plane_pack(P + o_band, nullptr, rw, b - a, false, rule, dst[0], out[0].pitch, a - y0, c.s);
-    }
-    HIP_TRY(hipGetLastError());
-    return SRCNN_OK;
+        return SRCNN_OK;
+    });
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-// srcnn_pixel_io.h -- what the conversion kernels (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip, srcnn_rgb.hip) share: the
-// launch-time alignment test and grid size, the float4-or-scalar access to a piece of a tight float row, and the samples of
-// 8-bit / 16-bit words packed in consecutive dwords.  Internal, HIP only.
+// srcnn_pixel_io.h -- what the conversion kernels (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip, srcnn_rgb.hip and the window
+// kernels) share of memory access: the launch-time alignment test and grid size, the float4-or-scalar access to a piece of a
+// tight float row, and the samples of 8-bit / 16-bit words packed in consecutive dwords.  (Their arithmetic is
+// srcnn_colour_rules.h.)  Internal, HIP only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -24,15 +24,29 @@ void launch_rgb_pack(const RgbRule& f, const float* const in[4], unsigned w, uns
 // window, with the Y line of launch_rgb_unpack.  No byte outside that rectangle is read.
 void launch_rgb_window_y(const RgbRule& f, const unsigned char* const src[4], const size_t pitch[4], unsigned sx0, unsigned sy0,
                          unsigned sw, unsigned sh, float* y, hipStream_t s);
-// Whether launch_rgb_window_merge serves output columns [x0, x0 + rw) and rows [gy0, gy0 + rows): the tables have host
-// copies and at most 8 taps, and the source patch of every 64 x 16 tile fits the kernel's LDS.
-bool rgb_window_merge_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned x0, unsigned rw, unsigned gy0, unsigned rows);
 // One band of the rect: Cb', Cr' (and A') of output columns [x0, x0 + rw) and rows [gy0, gy0 + rows) resampled from the whole
 // w x h integer source with the tables th (columns) and tv (rows), an up-scale in both axes, merged with yband (tight, rw floats
-// per row) as launch_rgb_pack merges, into rows [row0, row0 + rows) of dst (whose first pixel is the rect's) and of conv.
+// per row) as launch_rgb_pack merges, into rows [row0, row0 + rows) of dst (whose first pixel is the rect's) and of conv.  The
+// caller has asked window_tile_fits (srcnn_window_tile.h) for that range.
 void launch_rgb_window_merge(const RgbRule& f, const unsigned char* const src[4], const size_t spitch[4], unsigned w, unsigned h,
                              const float* yband, unsigned x0, unsigned gy0, unsigned rw, unsigned rows,
                              const DevAxisTable& th, const DevAxisTable& tv, unsigned char* const dst[4], const size_t dpitch[4],
                              unsigned row0, unsigned char* conv, size_t conv_pitch, hipStream_t s);
 
 }  // namespace srcnn
+
+// One launch of the <BPS, PLANAR, D> instance of an RGB kernel template that the rule f selects (blocks of 256 threads)
+#define RGB_DISPATCH(KERNEL, f, grid, s, a)                                                                                  \
+    do {                                                                                                                     \
+        const int sel = ((f).bps == 2 ? 4 : 0) | ((f).planar ? 2 : 0) | ((f).ch == 4 ? 1 : 0);                               \
+        switch (sel) {                                                                                                       \
+        case 0: hipLaunchKernelGGL((KERNEL<1, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
+        case 1: hipLaunchKernelGGL((KERNEL<1, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        case 2: hipLaunchKernelGGL((KERNEL<1, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
+        case 3: hipLaunchKernelGGL((KERNEL<1, true, 4>), grid, dim3(256), 0, s, a); break;                                   \
+        case 4: hipLaunchKernelGGL((KERNEL<2, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
+        case 5: hipLaunchKernelGGL((KERNEL<2, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        case 6: hipLaunchKernelGGL((KERNEL<2, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
+        default: hipLaunchKernelGGL((KERNEL<2, true, 4>), grid, dim3(256), 0, s, a); break;                                  \
+        }                                                                                                                    \
+    } while (0)

@@ -7,6 +7,7 @@
 //   k_rgb_pack     tight float32 rows Y', Cb', Cr' (and A') -> destination rows of the integer plane(s), and optionally the
 //                  truncated Y' plane; the merge of k_ycc_merge (src/libsrcnn.cpp:274-308), then
 //                  sample = (unsigned)(MAX(0, MIN(255, v)) * 2^s) in the reference's macro forms
+// The split, the merge and the sample code are srcnn_colour_rules.h, shared with the window kernels of srcnn_rgb_window.hip.
 //
 // Both kernels are memory-bound and move 4 pixels per thread: the float side as one 16-byte access per plane, the integer
 // side as the 1 .. 8 consecutive dwords that hold the 4 pixels (12 / 16 / 24 / 32 bytes interleaved, 4 / 8 bytes per plane
@@ -17,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
 #include "srcnn_rgb.h"
 
@@ -40,13 +42,6 @@ struct RgbIo {
     int bgr;
     int int_vec, flt_vec, conv_vec;      // dword accesses of the integer planes / float4 accesses / dword stores of conv are aligned
 };
-
-__device__ __forceinline__ unsigned to_code(float v, float up)
-{   // MIN(255.f, v) then MAX(0.f, .) in the reference's macro forms, the exact scaling, the truncating cast
-    v = (255.f < v) ? 255.f : v;
-    v = (0.f > v) ? 0.f : v;
-    return (unsigned)(v * up);
-}
 
 template <int BPS, bool PLANAR, int D>
 __global__ __launch_bounds__(256) void k_rgb_unpack(const RgbIo a)
@@ -98,9 +93,9 @@ __global__ __launch_bounds__(256) void k_rgb_unpack(const RgbIo a)
 #pragma unroll
             for (int k = 0; k < D; ++k) ch[k] = (float)(v[px][k] & a.mask) * a.down;
             const float r_ = a.bgr ? ch[2] : ch[0], g = ch[1], b = a.bgr ? ch[0] : ch[2];
-            yv[px] = (0.299f * r_) + (0.587f * g) + (0.114f * b);                 // src/libsrcnn.cpp:251-256
-            cbv[px] = 128.f - (0.1687f * r_) - (0.3313f * g) + (0.5f * b);
-            crv[px] = 128.f + (0.5f * r_) - (0.4187f * g) - (0.0813f * b);
+            yv[px] = split_y(r_, g, b);
+            cbv[px] = split_cb(r_, g, b);
+            crv[px] = split_cr(r_, g, b);
             av[px] = ch[3];
         }
         const size_t o = (size_t)r * a.w + c;
@@ -141,10 +136,10 @@ __global__ __launch_bounds__(256) void k_rgb_pack(const RgbIo a)
         unsigned code[kChunkRgb][D], cv[kChunkRgb];              // [pixel][channel in memory order]
 #pragma unroll
         for (int px = 0; px < (int)kChunkRgb; ++px) {
-            const float fy = yv[px], cb = cbv[px] - 128.f, cr = crv[px] - 128.f;   // src/libsrcnn.cpp:287-307
-            const unsigned R = to_code(fy + 45.f * cr / 32.f, a.up);
-            const unsigned G = to_code(fy - (11.f * cb + 23.f * cr) / 32.f, a.up);
-            const unsigned B = to_code(fy + 113.f * cb / 64.f, a.up);
+            const float fy = yv[px], cb = cbv[px] - 128.f, cr = crv[px] - 128.f;
+            const unsigned R = to_code(merge_r(fy, cr), a.up);
+            const unsigned G = to_code(merge_g(fy, cb, cr), a.up);
+            const unsigned B = to_code(merge_b(fy, cb), a.up);
             code[px][0] = a.bgr ? B : R;
             code[px][1] = G;
             code[px][2] = a.bgr ? R : B;
@@ -220,21 +215,6 @@ RgbIo io_of(const RgbRule& f, unsigned char* const p[4], const size_t pitch[4], 
     a.mask = f.mask; a.down = f.down; a.up = f.up; a.bgr = f.bgr ? 1 : 0;
     return a;
 }
-
-#define RGB_DISPATCH(KERNEL, f, grid, s, a)                                                                                  \
-    do {                                                                                                                     \
-        const int sel = ((f).bps == 2 ? 4 : 0) | ((f).planar ? 2 : 0) | ((f).ch == 4 ? 1 : 0);                               \
-        switch (sel) {                                                                                                       \
-        case 0: hipLaunchKernelGGL((KERNEL<1, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
-        case 1: hipLaunchKernelGGL((KERNEL<1, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        case 2: hipLaunchKernelGGL((KERNEL<1, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
-        case 3: hipLaunchKernelGGL((KERNEL<1, true, 4>), grid, dim3(256), 0, s, a); break;                                   \
-        case 4: hipLaunchKernelGGL((KERNEL<2, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
-        case 5: hipLaunchKernelGGL((KERNEL<2, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        case 6: hipLaunchKernelGGL((KERNEL<2, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
-        default: hipLaunchKernelGGL((KERNEL<2, true, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        }                                                                                                                    \
-    } while (0)
 
 }  // namespace
 

@@ -6,31 +6,19 @@
 //                        needs the 6-sample halo, chroma does not
 //   k_rgb_window_merge   one launch per band: Cb', Cr' (and A') of a 64 x 16 tile of the rect resampled straight from the
 //                        integer source, merged with the finished Y' rows and written in the caller's format (and the
-//                        truncated Y' plane): split of k_rgb_unpack -> the two passes of k_win_cols / k_win_rows -> merge and
-//                        to_code of k_rgb_pack, with that kernel's vector / scalar stores
+//                        truncated Y' plane): split of k_rgb_unpack -> the tile resampler (srcnn_window_tile.h, which describes
+//                        its four steps and says which shapes it serves) -> merge and to_code of k_rgb_pack, with that kernel's
+//                        vector / scalar stores
 //
-// k_rgb_window_merge serves up-scales in both axes with contribution tables of at most 8 taps (the host checks that every
-// tile's source patch fits kPatchW x kPatchH: rgb_window_merge_fits); everything else takes the plane route of rgb_rect
-// (srcnn_frames.cpp), which needs no kernel of its own.  A workgroup
-//   1. reads the first / last tap of its columns and rows off the tables (LDS min / max): the source patch of the tile,
-//   2. stages split Cb, Cr (and A) of the patch in LDS as floats,
-//   3. runs the vertical pass into an fp32 intermediate of 16 rows x patch columns (the pass order and the rounded
-//      intermediate of resample_window for an up-scale),
-//   4. runs the horizontal pass for 4 consecutive pixels per thread, merges them with Y' and stores them.
-// Both passes are acc = 0.0; acc = acc + wt[t] * (double)px in tap order; one (float)acc -- the operations of
-// k_resample_cols / k_resample_rows, so the tile holds the bits the plane resamplers put at the same place.  The tap count
-// of the vertical pass is uniform over a row of the tile; at 2x two neighbouring columns of the horizontal pass read the same
-// LDS words (a broadcast), and the 4 rows a wave covers lie kPatchW = 72 words = 8 banks apart.
-//
-// Every index is bounded: the patch is clamped to the w x h source, LDS indices lie inside the extents the host checked, and a
-// thread stores only pixels of its tile that lie inside the rect.
+// The pixel rules are srcnn_colour_rules.h, shared with srcnn_rgb.hip.  A thread stores only pixels of its tile that lie inside
+// the rect.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
+#include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
 #include "srcnn_rgb.h"
+#include "srcnn_window_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -38,9 +26,7 @@ namespace srcnn {
 
 namespace {
 
-constexpr unsigned kChunk = 4;                   // pixels per thread
-constexpr int kTileW = 64, kTileH = 16;          // the tile of the layer kernels
-constexpr int kPatchW = kTileW + 8, kPatchH = kTileH + 8;
+constexpr unsigned kChunk = kTileChunk;          // pixels per thread, of both kernels
 
 struct WinY {
     const unsigned char* p[4];                   // integer planes at the window's first sample (interleaved: p[0] only)
@@ -64,19 +50,11 @@ struct WinMerge {
     unsigned row0;                               // row of the rect at which the band starts
     unsigned rw, rows;                           // columns of the rect, rows of the band
     unsigned w, h;                               // source size
-    const int* hf; const int* ht; const double* hw; int hstride;     // horizontal table (dw <- w)
-    const int* vf; const int* vt; const double* vw; int vstride;     // vertical table (dh <- h)
+    TileTables t;                                // horizontal table (dw <- w), vertical table (dh <- h)
     unsigned mask;
     float down, up;
     int bgr, int_vec, conv_vec;
 };
-
-__device__ __forceinline__ unsigned to_code(float v, float up)
-{   // as k_rgb_pack: MIN(255.f, v) then MAX(0.f, .) in the reference's macro forms, the exact scaling, the truncating cast
-    v = (255.f < v) ? 255.f : v;
-    v = (0.f > v) ? 0.f : v;
-    return (unsigned)(v * up);
-}
 
 template <int BPS, bool PLANAR, int D>
 __global__ __launch_bounds__(256) void k_rgb_window_y(const WinY a)
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(256) void k_rgb_window_y(const WinY a)
 #pragma unroll
             for (int k = 0; k < 3; ++k) ch[k] = (float)(v[px][k] & a.mask) * a.down;
             const float r_ = a.bgr ? ch[2] : ch[0], g = ch[1], b = a.bgr ? ch[0] : ch[2];
-            yv[px] = (0.299f * r_) + (0.587f * g) + (0.114f * b);                 // src/libsrcnn.cpp:251-256
+            yv[px] = split_y(r_, g, b);
         }
         store_floats<kChunk>(a.y + (size_t)r * a.w + c, yv, n, a.flt_vec);
     }
@@ -146,26 +124,9 @@ __global__ __launch_bounds__(256) void k_rgb_window_merge(const WinMerge a)
     const int ncol = (int)min((unsigned)kTileW, a.rw - tx), nrow = (int)min((unsigned)kTileH, a.rows - ty);
     const unsigned gx = a.x0 + tx, gy = a.gy0 + ty;                          // the tile inside the dw x dh output
 
-    // 1. the source patch of the tile, off the tables
-    if (tid == 0) { s_span[0] = 0x7fffffff; s_span[1] = 0; s_span[2] = 0x7fffffff; s_span[3] = 0; }
-    __syncthreads();
-    if (tid < ncol) {
-        const int f = a.hf[gx + tid];
-        atomicMin(&s_span[0], f);
-        atomicMax(&s_span[1], f + a.ht[gx + tid]);
-    } else if (tid >= kTileW && tid - kTileW < nrow) {
-        const int f = a.vf[gy + (tid - kTileW)];
-        atomicMin(&s_span[2], f);
-        atomicMax(&s_span[3], f + a.vt[gy + (tid - kTileW)]);
-    }
-    __syncthreads();
-    const int c_lo = max(s_span[0], 0), r_lo = max(s_span[2], 0);
-    const int pw = min(min(s_span[1], (int)a.w) - c_lo, kPatchW), ph = min(min(s_span[3], (int)a.h) - r_lo, kPatchH);
-
-    // 2. split Cb, Cr (and A) of the patch
-    for (int i = tid; i < pw * ph; i += 256) {
-        const int pr = i / pw, pc = i - pr * pw;
-        const size_t sr = (size_t)(r_lo + pr), sc = (size_t)(c_lo + pc);
+    // 1. - 3. (srcnn_window_tile.h); a staged sample is the split Cb, Cr (and A) of a source pixel
+    const TilePatch p = tile_patch(a.t, s_span, tid, gx, gy, ncol, nrow, a.w, a.h);
+    tile_stage<NC>(s_patch, p, tid, [&](size_t sr, size_t sc, float* v) {
         float ch[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int k = 0; k < D; ++k) {
@@ -173,29 +134,12 @@ __global__ __launch_bounds__(256) void k_rgb_window_merge(const WinMerge a)
             ch[k] = (float)(load_scalar<BPS>(q) & a.mask) * a.down;
         }
         const float r_ = a.bgr ? ch[2] : ch[0], g = ch[1], b = a.bgr ? ch[0] : ch[2];
-        s_patch[0][pr][pc] = 128.f - (0.1687f * r_) - (0.3313f * g) + (0.5f * b);       // src/libsrcnn.cpp:251-256
-        s_patch[1][pr][pc] = 128.f + (0.5f * r_) - (0.4187f * g) - (0.0813f * b);
-        if constexpr (D == 4) s_patch[2][pr][pc] = ch[3];
-    }
+        v[0] = split_cb(r_, g, b);
+        v[1] = split_cr(r_, g, b);
+        if constexpr (D == 4) v[2] = ch[3];
+    });
     __syncthreads();
-
-    // 3. vertical pass: rows of the tile x columns of the patch
-    for (int i = tid; i < nrow * pw; i += 256) {
-        const int ry = i / pw, pc = i - ry * pw;
-        const unsigned y = gy + ry;
-        const int s0 = a.vf[y] - r_lo, n = a.vt[y];
-        const double* wr = a.vw + (size_t)y * a.vstride;
-        if (s0 < 0 || s0 + n > kPatchH) continue;            // (never: rgb_window_merge_fits)
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            double acc = 0.0;
-            for (int t = 0; t < n; ++t) {
-                const double px = (double)s_patch[k][s0 + t][pc];
-                acc = acc + wr[t] * px;
-            }
-            s_mid[k][ry][pc] = (float)acc;
-        }
-    }
+    tile_vertical<NC>(a.t, s_patch, s_mid, p, tid, gy, nrow);
     __syncthreads();
 
     // 4. horizontal pass, merge, store: 4 consecutive pixels of one row per thread
@@ -211,23 +155,13 @@ __global__ __launch_bounds__(256) void k_rgb_window_merge(const WinMerge a)
         float rs[3] = {128.f, 128.f, 0.f};
         float fy = 0.f;
         if ((unsigned)px < n) {
-            const unsigned x = gx + c + px;
-            const int s0 = a.hf[x] - c_lo, nt = a.ht[x];
-            const double* wr = a.hw + (size_t)x * a.hstride;
-            if (s0 >= 0 && s0 + nt <= kPatchW) {             // (always: rgb_window_merge_fits)
-#pragma unroll
-                for (int k = 0; k < NC; ++k) {
-                    double acc = 0.0;
-                    for (int t = 0; t < nt; ++t) acc = acc + wr[t] * (double)s_mid[k][ry][s0 + t];
-                    rs[k] = (float)acc;
-                }
-            }
+            tile_horizontal<NC>(a.t, s_mid, p, ry, gx + c + px, rs);
             fy = a.y[br * a.rw + dc + px];
         }
-        const float cb = rs[0] - 128.f, cr = rs[1] - 128.f;                      // src/libsrcnn.cpp:287-307
-        const unsigned R = to_code(fy + 45.f * cr / 32.f, a.up);
-        const unsigned G = to_code(fy - (11.f * cb + 23.f * cr) / 32.f, a.up);
-        const unsigned B = to_code(fy + 113.f * cb / 64.f, a.up);
+        const float cb = rs[0] - 128.f, cr = rs[1] - 128.f;
+        const unsigned R = to_code(merge_r(fy, cr), a.up);
+        const unsigned G = to_code(merge_g(fy, cb, cr), a.up);
+        const unsigned B = to_code(merge_b(fy, cb), a.up);
         code[px][0] = a.bgr ? B : R;
         code[px][1] = G;
         code[px][2] = a.bgr ? R : B;
@@ -282,36 +216,6 @@ __global__ __launch_bounds__(256) void k_rgb_window_merge(const WinMerge a)
     }
 }
 
-#define RGB_WINDOW_DISPATCH(KERNEL, f, grid, s, a)                                                                           \
-    do {                                                                                                                     \
-        const int sel = ((f).bps == 2 ? 4 : 0) | ((f).planar ? 2 : 0) | ((f).ch == 4 ? 1 : 0);                               \
-        switch (sel) {                                                                                                       \
-        case 0: hipLaunchKernelGGL((KERNEL<1, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
-        case 1: hipLaunchKernelGGL((KERNEL<1, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        case 2: hipLaunchKernelGGL((KERNEL<1, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
-        case 3: hipLaunchKernelGGL((KERNEL<1, true, 4>), grid, dim3(256), 0, s, a); break;                                   \
-        case 4: hipLaunchKernelGGL((KERNEL<2, false, 3>), grid, dim3(256), 0, s, a); break;                                  \
-        case 5: hipLaunchKernelGGL((KERNEL<2, false, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        case 6: hipLaunchKernelGGL((KERNEL<2, true, 3>), grid, dim3(256), 0, s, a); break;                                   \
-        default: hipLaunchKernelGGL((KERNEL<2, true, 4>), grid, dim3(256), 0, s, a); break;                                  \
-        }                                                                                                                    \
-    } while (0)
-
-// the extent of source indices that `count` destination indices from `first` read, tile by tile of `tile` of them, fits `cap`
-bool axis_tiles_fit(const DevAxisTable& t, unsigned first, unsigned count, unsigned tile, int cap)
-{
-    if (!t.h_first || !t.h_taps || t.max_taps > 8) return false;
-    for (unsigned a = 0; a < count; a += tile) {
-        int lo = 0x7fffffff, hi = 0;
-        for (unsigned u = first + a; u < first + std::min(count, a + tile); ++u) {
-            lo = std::min(lo, t.h_first[u]);
-            hi = std::max(hi, t.h_first[u] + t.h_taps[u]);
-        }
-        if (lo < 0 || hi - lo > cap) return false;
-    }
-    return true;
-}
-
 }  // namespace
 
 void launch_rgb_window_y(const RgbRule& f, const unsigned char* const src[4], const size_t pitch[4], unsigned sx0, unsigned sy0,
@@ -331,12 +235,7 @@ void launch_rgb_window_y(const RgbRule& f, const unsigned char* const src[4], co
     a.w = sw; a.rows = sh;
     a.mask = f.mask; a.down = f.down; a.bgr = f.bgr ? 1 : 0;
     const dim3 grid = grid_for((size_t)((sw + kChunk - 1) / kChunk) * sh, 8192);
-    RGB_WINDOW_DISPATCH(k_rgb_window_y, f, grid, s, a);
-}
-
-bool rgb_window_merge_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned x0, unsigned rw, unsigned gy0, unsigned rows)
-{
-    return axis_tiles_fit(th, x0, rw, kTileW, kPatchW) && axis_tiles_fit(tv, gy0, rows, kTileH, kPatchH);
+    RGB_DISPATCH(k_rgb_window_y, f, grid, s, a);
 }
 
 void launch_rgb_window_merge(const RgbRule& f, const unsigned char* const src[4], const size_t spitch[4], unsigned w, unsigned h,
@@ -357,11 +256,10 @@ void launch_rgb_window_merge(const RgbRule& f, const unsigned char* const src[4]
     a.conv_vec = conv && aligned_to(conv, 4) && conv_pitch % 4 == 0;
     a.y = yband;
     a.x0 = x0; a.gy0 = gy0; a.row0 = row0; a.rw = rw; a.rows = rows; a.w = w; a.h = h;
-    a.hf = th.first; a.ht = th.taps; a.hw = th.weight; a.hstride = th.stride;
-    a.vf = tv.first; a.vt = tv.taps; a.vw = tv.weight; a.vstride = tv.stride;
+    a.t = tile_tables(th, tv);
     a.mask = f.mask; a.down = f.down; a.up = f.up; a.bgr = f.bgr ? 1 : 0;
     const dim3 grid((rw + kTileW - 1) / kTileW, (rows + kTileH - 1) / kTileH);
-    RGB_WINDOW_DISPATCH(k_rgb_window_merge, f, grid, s, a);
+    RGB_DISPATCH(k_rgb_window_merge, f, grid, s, a);
 }
 
 }  // namespace srcnn

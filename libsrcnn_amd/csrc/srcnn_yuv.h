@@ -24,13 +24,11 @@ void launch_plane_pack(const float* s0, const float* s1, unsigned w, unsigned ro
                        unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s);
 
 // ---- the window form behind the rect call (srcnn_yuv_window.hip; include/srcnn_amd_yuv_rect.h) ----
-// Whether launch_yuv_window_chroma serves chroma output columns [cx0, cx0 + cols) and rows [cy0, cy0 + rows): the tables have
-// host copies and at most 8 taps, and the source patch of every 64 x 16 tile fits the kernel's LDS.
-bool yuv_window_chroma_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned cx0, unsigned cols, unsigned cy0, unsigned rows);
 // U' and V' of chroma output columns [cx0, cx0 + cols) and rows [cy0, cy0 + rows) resampled from the WHOLE cw x ch integer
 // chroma plane(s) src with the tables th (columns) and tv (rows), an up-scale in both axes, saturated and written as
 // launch_plane_pack writes chroma, into dst, whose first sample is the rect's.  semi: src[0] / dst[0] hold (U, V) pairs, else
 // src[0] / dst[0] are U and src[1] / dst[1] V.  f as for launch_plane_unpack.  No source byte outside the taps' span is read.
+// The caller has asked window_tile_fits (srcnn_window_tile.h) for that range.
 void launch_yuv_window_chroma(const unsigned char* const src[2], const size_t spitch[2], unsigned cw, unsigned ch, bool semi,
                               const Yuv16Rule* f, unsigned cx0, unsigned cy0, unsigned cols, unsigned rows, const DevAxisTable& th,
                               const DevAxisTable& tv, unsigned char* const dst[2], const size_t dpitch[2], hipStream_t s);

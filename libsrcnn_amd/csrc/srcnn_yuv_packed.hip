@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
 #include "srcnn_yuv.h"
 
@@ -52,13 +53,8 @@ enum { kIoVec = 0, kIoDword = 4, kIoWord = 2, kIoByte = 1 };
 template <bool SAT>
 __device__ __forceinline__ unsigned to_word(float v, float scale, float maxv)
 {
-    if constexpr (SAT) {                 // MIN(maxv, v) then MAX(0.f, .) then truncating cast, in the reference's macro forms
-        v = (maxv < v) ? maxv : v;
-        v = (0.f > v) ? 0.f : v;
-        return (unsigned)v;
-    } else {
-        return (unsigned)(v * scale);
-    }
+    if constexpr (SAT) return (unsigned)saturate(v, maxv);
+    else return (unsigned)(v * scale);
 }
 
 __device__ __forceinline__ unsigned load_dword(const unsigned char* p, int io)

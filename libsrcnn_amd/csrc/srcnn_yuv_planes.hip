@@ -11,6 +11,7 @@
 //                                               v to [0, 255], like conv_opt in k_ycc_merge (src/libsrcnn.cpp:889-905)
 //                                U', V' (SAT):  MIN(maxv), MAX(0), truncation on the native scale, << lshift: the reference's
 //                                               macro forms, as to_u8_sat in srcnn_kernels.hip
+// The saturation and the word read are srcnn_colour_rules.h, shared with the window kernel of srcnn_yuv_window.hip.
 //
 // rshift, mask, lshift, maxv and scale are kernel arguments, so every depth and both alignments run the same few 16-bit
 // instances; the 8-bit instances compile them out.  Both kernels are memory-bound and move 4 * BPS samples per thread and
@@ -20,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
 #include "srcnn_yuv.h"
 
@@ -32,19 +34,9 @@ namespace {
 template <int BPS, bool SAT>
 __device__ __forceinline__ unsigned to_sample(float v, float scale, float maxv, unsigned lshift)
 {
-    if constexpr (BPS == 1) {
-        if constexpr (SAT) {             // MIN(255.f, v) then MAX(0.f, .) then truncating cast, in the reference's macro forms
-            v = (255.f < v) ? 255.f : v;
-            v = (0.f > v) ? 0.f : v;
-        }
-        return (unsigned char)v;
-    } else if constexpr (SAT) {
-        v = (maxv < v) ? maxv : v;
-        v = (0.f > v) ? 0.f : v;
-        return (unsigned)v << lshift;
-    } else {
-        return (unsigned)(v * scale) << lshift;
-    }
+    if constexpr (SAT) return to_saturated_sample<BPS>(v, maxv, lshift);
+    else if constexpr (BPS == 1) return (unsigned char)v;
+    else return (unsigned)(v * scale) << lshift;
 }
 
 // ND consecutive dwords as the widest accesses they allow: a dword, a uint2 or uint4s
@@ -112,7 +104,7 @@ __global__ __launch_bounds__(256) void k_plane_unpack(const unsigned char* __res
 #pragma unroll
         for (unsigned k = 0; k < N; ++k) {
             if constexpr (BPS == 1) { fa[k] = (float)a[k]; fb[k] = (float)b[k]; }
-            else { fa[k] = (float)((a[k] >> rshift) & mask) * scale; fb[k] = (float)((b[k] >> rshift) & mask) * scale; }
+            else { fa[k] = (float)word_value(a[k], rshift, mask) * scale; fb[k] = (float)word_value(b[k], rshift, mask) * scale; }
         }
         const size_t o = (size_t)r * w + c;
         if (n == N && dst_vec) {

@@ -3,30 +3,21 @@
 // rect and without a float chroma plane.
 //
 //   k_yuv_window_chroma   one launch per rect: U' and V' of a 64 x 16 tile of the chroma rect resampled straight from the
-//                         integer source and written in the caller's format: the read rule of k_plane_unpack -> the two passes
-//                         of k_win_cols / k_win_rows -> to_sample and the write rule of k_plane_pack.  Planar: two source and
-//                         two destination planes; semi-planar: one plane of (U, V) pairs, de-interleaved on the way in and
-//                         interleaved on the way out.
+//                         integer source and written in the caller's format: the read rule of k_plane_unpack (16-bit words:
+//                         word_value, on the native scale) -> the tile resampler (srcnn_window_tile.h, which describes its four
+//                         steps and says which shapes it serves; here on the CHROMA grid: dcw > cw and dch > ch) -> the
+//                         saturation and the write rule of k_plane_pack.  Planar: two source and two destination planes;
+//                         semi-planar: one plane of (U, V) pairs, de-interleaved on the way in and interleaved on the way out.
 //
-// It serves chroma up-scales in both axes (on the CHROMA grid: dcw > cw and dch > ch) with contribution tables of at most 8
-// taps (the host checks that every tile's source patch fits kPatchW x kPatchH: yuv_window_chroma_fits); everything else takes
-// the plane route of yuv_rect (srcnn_frames.cpp), which needs no kernel of its own.  A workgroup
-//   1. reads the first / last tap of its columns and rows off the tables (LDS min / max): the source patch of the tile,
-//   2. stages U and V of the patch in LDS as floats (16-bit words: (word >> rshift) & mask, on the native scale),
-//   3. runs the vertical pass into an fp32 intermediate of 16 rows x patch columns (the pass order and the rounded
-//      intermediate of resample_window for an up-scale),
-//   4. runs the horizontal pass for 4 consecutive samples per thread, saturates and stores them.
-// Both passes are acc = 0.0; acc = acc + wt[t] * (double)px in tap order; one (float)acc -- the operations of
-// k_resample_cols / k_resample_rows, so the tile holds the bits the plane resamplers put at the same place.
-//
-// Every index is bounded: the patch is clamped to the cw x ch source, LDS indices lie inside the extents the host checked, and
-// a thread stores only samples of its tile that lie inside the chroma rect.  A thread's 4 samples (4 pairs) go out as one
-// 4- / 8- / 16-byte store where the plane's base and pitch are multiples of that size, else sample by sample.
+// The pixel rules are srcnn_colour_rules.h, shared with srcnn_yuv_planes.hip.  A thread stores only samples of its tile that lie
+// inside the chroma rect.  Its 4 samples (4 pairs) go out as one 4- / 8- / 16-byte store where the plane's base and pitch are
+// multiples of that size, else sample by sample.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
-#include "srcnn_rgb.h"
+#include "srcnn_window_tile.h"
 #include "srcnn_yuv.h"
 
 #pragma clang fp contract(off)
@@ -35,9 +26,7 @@ namespace srcnn {
 
 namespace {
 
-constexpr unsigned kChunk = 4;                   // samples per thread and plane
-constexpr int kTileW = 64, kTileH = 16;          // as k_rgb_window_merge (srcnn_rgb_window.hip): rgb_window_merge_fits is its predicate
-constexpr int kPatchW = kTileW + 8, kPatchH = kTileH + 8;
+constexpr unsigned kChunk = kTileChunk;          // samples per thread and plane
 
 struct WinChroma {
     const unsigned char* sp[2];                  // the WHOLE source chroma planes (semi-planar: sp[0] only)
@@ -47,32 +36,17 @@ struct WinChroma {
     unsigned cx0, cy0;                           // the chroma rect inside the dcw x dch chroma output
     unsigned cols, rows;
     unsigned w, h;                               // source chroma size (cw x ch)
-    const int* hf; const int* ht; const double* hw; int hstride;     // horizontal table (dcw <- cw)
-    const int* vf; const int* vt; const double* vw; int vstride;     // vertical table (dch <- ch)
+    TileTables t;                                // horizontal table (dcw <- cw), vertical table (dch <- ch)
     unsigned rshift, mask, lshift;               // 16-bit words: read (word >> rshift) & mask, write value << lshift
     float maxv;
     int dst_vec;
 };
 
 template <int BPS>
-__device__ __forceinline__ unsigned to_chroma(float v, float maxv, unsigned lshift)
-{   // as to_sample<BPS, true> of k_plane_pack: MIN(maxv, v) then MAX(0.f, .) in the reference's macro forms, the truncating cast
-    if constexpr (BPS == 1) {
-        v = (255.f < v) ? 255.f : v;
-        v = (0.f > v) ? 0.f : v;
-        return (unsigned char)v;
-    } else {
-        v = (maxv < v) ? maxv : v;
-        v = (0.f > v) ? 0.f : v;
-        return (unsigned)v << lshift;
-    }
-}
-
-template <int BPS>
 __device__ __forceinline__ float chroma_in(const unsigned char* q, unsigned rshift, unsigned mask)
-{   // as k_plane_unpack with scale 1
+{
     if constexpr (BPS == 1) return (float)load_scalar<1>(q);
-    else return (float)((load_scalar<2>(q) >> rshift) & mask);
+    else return (float)word_value(load_scalar<2>(q), rshift, mask);
 }
 
 // ND dwords at p as ONE store (p is aligned to 4 * ND bytes)
@@ -99,50 +73,16 @@ __global__ __launch_bounds__(256) void k_yuv_window_chroma(const WinChroma a)
     const int ncol = (int)min((unsigned)kTileW, a.cols - tx), nrow = (int)min((unsigned)kTileH, a.rows - ty);
     const unsigned gx = a.cx0 + tx, gy = a.cy0 + ty;                         // the tile inside the dcw x dch chroma output
 
-    // 1. the source patch of the tile, off the tables
-    if (tid == 0) { s_span[0] = 0x7fffffff; s_span[1] = 0; s_span[2] = 0x7fffffff; s_span[3] = 0; }
-    __syncthreads();
-    if (tid < ncol) {
-        const int f = a.hf[gx + tid];
-        atomicMin(&s_span[0], f);
-        atomicMax(&s_span[1], f + a.ht[gx + tid]);
-    } else if (tid >= kTileW && tid - kTileW < nrow) {
-        const int f = a.vf[gy + (tid - kTileW)];
-        atomicMin(&s_span[2], f);
-        atomicMax(&s_span[3], f + a.vt[gy + (tid - kTileW)]);
-    }
-    __syncthreads();
-    const int c_lo = max(s_span[0], 0), r_lo = max(s_span[2], 0);
-    const int pw = min(min(s_span[1], (int)a.w) - c_lo, kPatchW), ph = min(min(s_span[3], (int)a.h) - r_lo, kPatchH);
-
-    // 2. U and V of the patch
-    for (int i = tid; i < pw * ph; i += 256) {
-        const int pr = i / pw, pc = i - pr * pw;
-        const size_t sr = (size_t)(r_lo + pr), sc = (size_t)(c_lo + pc);
+    // 1. - 3. (srcnn_window_tile.h); a staged sample is U and V of a source column
+    const TilePatch p = tile_patch(a.t, s_span, tid, gx, gy, ncol, nrow, a.w, a.h);
+    tile_stage<2>(s_patch, p, tid, [&](size_t sr, size_t sc, float* v) {
         const unsigned char* qu = a.sp[0] + sr * a.spitch[0] + sc * SPP * BPS;
         const unsigned char* qv = SEMI ? qu + BPS : a.sp[1] + sr * a.spitch[1] + sc * BPS;
-        s_patch[0][pr][pc] = chroma_in<BPS>(qu, a.rshift, a.mask);
-        s_patch[1][pr][pc] = chroma_in<BPS>(qv, a.rshift, a.mask);
-    }
+        v[0] = chroma_in<BPS>(qu, a.rshift, a.mask);
+        v[1] = chroma_in<BPS>(qv, a.rshift, a.mask);
+    });
     __syncthreads();
-
-    // 3. vertical pass: rows of the tile x columns of the patch
-    for (int i = tid; i < nrow * pw; i += 256) {
-        const int ry = i / pw, pc = i - ry * pw;
-        const unsigned y = gy + ry;
-        const int s0 = a.vf[y] - r_lo, n = a.vt[y];
-        const double* wr = a.vw + (size_t)y * a.vstride;
-        if (s0 < 0 || s0 + n > kPatchH) continue;            // (never: yuv_window_chroma_fits)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            double acc = 0.0;
-            for (int t = 0; t < n; ++t) {
-                const double px = (double)s_patch[k][s0 + t][pc];
-                acc = acc + wr[t] * px;
-            }
-            s_mid[k][ry][pc] = (float)acc;
-        }
-    }
+    tile_vertical<2>(a.t, s_patch, s_mid, p, tid, gy, nrow);
     __syncthreads();
 
     // 4. horizontal pass, saturate, store: 4 consecutive samples of one row per thread
@@ -155,21 +95,9 @@ __global__ __launch_bounds__(256) void k_yuv_window_chroma(const WinChroma a)
 #pragma unroll
     for (int px = 0; px < (int)kChunk; ++px) {
         float rs[2] = {0.f, 0.f};
-        if ((unsigned)px < n) {
-            const unsigned x = gx + c + px;
-            const int s0 = a.hf[x] - c_lo, nt = a.ht[x];
-            const double* wr = a.hw + (size_t)x * a.hstride;
-            if (s0 >= 0 && s0 + nt <= kPatchW) {             // (always: yuv_window_chroma_fits)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    double acc = 0.0;
-                    for (int t = 0; t < nt; ++t) acc = acc + wr[t] * (double)s_mid[k][ry][s0 + t];
-                    rs[k] = (float)acc;
-                }
-            }
-        }
-        code[0][px] = to_chroma<BPS>(rs[0], a.maxv, a.lshift);
-        code[1][px] = to_chroma<BPS>(rs[1], a.maxv, a.lshift);
+        if ((unsigned)px < n) tile_horizontal<2>(a.t, s_mid, p, ry, gx + c + px, rs);
+        code[0][px] = to_saturated_sample<BPS>(rs[0], a.maxv, a.lshift);
+        code[1][px] = to_saturated_sample<BPS>(rs[1], a.maxv, a.lshift);
     }
     if (n == kChunk && a.dst_vec) {
         if constexpr (SEMI) {
@@ -200,11 +128,6 @@ __global__ __launch_bounds__(256) void k_yuv_window_chroma(const WinChroma a)
 
 }  // namespace
 
-bool yuv_window_chroma_fits(const DevAxisTable& th, const DevAxisTable& tv, unsigned cx0, unsigned cols, unsigned cy0, unsigned rows)
-{
-    return rgb_window_merge_fits(th, tv, cx0, cols, cy0, rows);      // the same tile, the same patch
-}
-
 void launch_yuv_window_chroma(const unsigned char* const src[2], const size_t spitch[2], unsigned cw, unsigned ch, bool semi,
                               const Yuv16Rule* f, unsigned cx0, unsigned cy0, unsigned cols, unsigned rows, const DevAxisTable& th,
                               const DevAxisTable& tv, unsigned char* const dst[2], const size_t dpitch[2], hipStream_t s)
@@ -219,8 +142,7 @@ void launch_yuv_window_chroma(const unsigned char* const src[2], const size_t sp
         a.dst_vec = a.dst_vec && aligned_to(dst[k], chunk) && dpitch[k] % chunk == 0;
     }
     a.cx0 = cx0; a.cy0 = cy0; a.cols = cols; a.rows = rows; a.w = cw; a.h = ch;
-    a.hf = th.first; a.ht = th.taps; a.hw = th.weight; a.hstride = th.stride;
-    a.vf = tv.first; a.vt = tv.taps; a.vw = tv.weight; a.vstride = tv.stride;
+    a.t = tile_tables(th, tv);
     a.rshift = f ? f->rshift : 0; a.mask = f ? f->mask : 0xffu; a.lshift = f ? f->lshift : 0;
     a.maxv = f ? (float)f->mask : 255.f;
     const dim3 grid((cols + kTileW - 1) / kTileW, (rows + kTileH - 1) / kTileH);

@@ -7,7 +7,10 @@
 //   * libsrcnn_amd/csrc/srcnn_frame_args.hpp    check_yuv_rect_args, the argument half of srcnn_yuv_upscale_rect_dev: odd
 //     origins, rects outside the output, sums that wrap in 32 bits, pitches, odd addresses, and the end-of-plane pointer
 //     arithmetic of the overlap rules -- a rect repainted inside the surface it is read from, two planes of the rect over each
-//     other -- on host buffers, with the sizes written out here.
+//     other -- on host buffers, with the sizes written out here;
+//   * libsrcnn_amd/csrc/srcnn_window_tile.h     window_tile_fits, the predicate that sends a rect's chroma through the fused tile
+//     kernels (k_rgb_window_merge, k_yuv_window_chroma) or down the plane route, on tables from build_axis_table: true for every
+//     chroma table of an up-scale, false for more than 8 taps, for tables without host copies and for a tile span beyond the patch.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +19,7 @@
 #include "../../include/srcnn_amd.h"
 #include "../../include/srcnn_amd_yuv_ex.h"
 #include "../../libsrcnn_amd/csrc/srcnn_rect_source.hpp"
+#include "../../libsrcnn_amd/csrc/srcnn_window_tile.h"
 
 // The product's fail() lives in srcnn_capi.cpp; this one formats as well, so the sanitizers see every message's arguments.
 namespace srcnn {
@@ -224,10 +228,67 @@ static void check_rect_args()
     }
 }
 
+static srcnn::TileAxis tile_axis(const srcnn::AxisTable& t) { return srcnn::TileAxis{t.first.data(), t.taps.data(), t.max_taps}; }
+
+// The route predicate.  Nothing observable says which route a rect took (both give the same bytes at the same cost), so a
+// predicate that refused everything would pass every other test: this is where it is held to its answers.
+static void check_window_tile_fits()
+{
+    using srcnn::build_axis_table;
+    using srcnn::window_tile_fits;
+    const float muls[] = {1.5f, 2.f, 2.5f, 3.f};
+    const unsigned lens[] = {9, 70, 97, 1920};
+    long n = 0;
+    for (int filter : {SRCNN_FILTER_NEAREST, SRCNN_FILTER_BILINEAR})         // (the only filters chroma_filter yields)
+        for (float mul : muls)
+            for (unsigned lh : lens)
+                for (unsigned lv : lens) {
+                    const unsigned dh = (unsigned)((float)lh * mul), dv = (unsigned)((float)lv * mul);
+                    const srcnn::AxisTable th = build_axis_table(filter, dh, lh), tv = build_axis_table(filter, dv, lv);
+                    CHECK(th.max_taps <= 8 && tv.max_taps <= 8, "filter %d x%g: %d / %d taps", filter, mul, th.max_taps, tv.max_taps);
+                    CHECK(window_tile_fits(tile_axis(th), tile_axis(tv), 0, dh, 0, dv), "filter %d x%g %ux%u: the whole output", filter, mul, lh, lv);
+                    // a rect that starts mid-tile and ends at the far border: its tiles straddle those of the whole output
+                    const unsigned x0 = dh > 37 ? 37 : dh / 2, y0 = dv > 5 ? 5 : dv / 2;
+                    CHECK(window_tile_fits(tile_axis(th), tile_axis(tv), x0, dh - x0, y0, dv - y0), "filter %d x%g %ux%u: rect at (%u,%u)", filter, mul,
+                          lh, lv, x0, y0);
+                    n += 2;
+                }
+    CHECK(n == 2 * 2 * 4 * 4 * 4, "%ld predicate calls", n);
+    const srcnn::AxisTable up = build_axis_table(SRCNN_FILTER_BILINEAR, 140, 70);
+    CHECK(window_tile_fits(tile_axis(up), tile_axis(up), 0, 140, 0, 140), "2x bilinear");
+    // more than 8 taps, in either axis: a 0.25x Lanczos table (whatever its spans)
+    const srcnn::AxisTable wide = build_axis_table(SRCNN_FILTER_LANCZOS3, 64, 256);
+    CHECK(wide.max_taps > 8, "0.25x Lanczos has %d taps", wide.max_taps);
+    CHECK(!window_tile_fits(tile_axis(wide), tile_axis(up), 0, 64, 0, 140) && !window_tile_fits(tile_axis(up), tile_axis(wide), 0, 140, 0, 64), "max_taps > 8");
+    srcnn::TileAxis many = tile_axis(up);
+    many.max_taps = 9;
+    CHECK(!window_tile_fits(many, tile_axis(up), 0, 140, 0, 140) && !window_tile_fits(tile_axis(up), many, 0, 140, 0, 140), "max_taps = 9 alone");
+    // no host copies
+    const srcnn::TileAxis none = {nullptr, nullptr, up.max_taps}, no_first = {nullptr, up.taps.data(), up.max_taps}, no_taps = {up.first.data(), nullptr, up.max_taps};
+    for (const srcnn::TileAxis& bad : {none, no_first, no_taps})
+        CHECK(!window_tile_fits(bad, tile_axis(up), 0, 140, 0, 140) && !window_tile_fits(tile_axis(up), bad, 0, 140, 0, 140), "NULL host arrays");
+    // a down-scale whose tile span exceeds the patch although its taps are few: 0.5x bilinear (5 taps; 64 outputs read about 130
+    // inputs, 16 about 34) and 0.25x nearest (1 tap; 64 outputs read about 253).  0.25x bilinear is refused as well, already for
+    // its 9 taps.
+    for (const srcnn::AxisTable& down : {build_axis_table(SRCNN_FILTER_BILINEAR, 960, 1920), build_axis_table(SRCNN_FILTER_NEAREST, 480, 1920)}) {
+        CHECK(down.max_taps <= 8, "filter %d to %u: %d taps", down.filter, down.dst_len, down.max_taps);
+        CHECK(!window_tile_fits(tile_axis(down), tile_axis(up), 0, down.dst_len, 0, 140), "columns to %u: 64 of them span more than %d", down.dst_len, srcnn::kPatchW);
+        CHECK(!window_tile_fits(tile_axis(up), tile_axis(down), 0, 140, 0, down.dst_len), "rows to %u: 16 of them span more than %d", down.dst_len, srcnn::kPatchH);
+        // ... and one tile of it alone already does, where a tile of the up-scale does not
+        CHECK(!srcnn::axis_tiles_fit(down.first.data(), down.taps.data(), down.max_taps, 64, 64, srcnn::kTileW, srcnn::kPatchW), "one tile to %u", down.dst_len);
+    }
+    CHECK(srcnn::axis_tiles_fit(up.first.data(), up.taps.data(), up.max_taps, 64, 64, srcnn::kTileW, srcnn::kPatchW), "one 2x tile");
+    const srcnn::AxisTable quarter = build_axis_table(SRCNN_FILTER_BILINEAR, 480, 1920);
+    CHECK(!window_tile_fits(tile_axis(quarter), tile_axis(up), 0, 480, 0, 140) && !window_tile_fits(tile_axis(up), tile_axis(quarter), 0, 140, 0, 480), "0.25x bilinear");
+    // an empty range asks nothing of the tables' contents
+    CHECK(window_tile_fits(tile_axis(up), tile_axis(up), 10, 0, 10, 0), "empty range");
+}
+
 int main()
 {
     check_source_rects();
     check_rect_args();
+    check_window_tile_fits();
     if (g_fail) {
         fprintf(stderr, "%d checks failed\n", g_fail);
         return 1;

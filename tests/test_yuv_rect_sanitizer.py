@@ -2,7 +2,9 @@
 
 tests/host/yuv_rect_sanitize.cpp is a stand-alone program (its own main, no GPU, no HIP) that drives srcnn_yuv_rect_source's
 body (csrc/srcnn_rect_source.hpp) and the argument validation of srcnn_yuv_upscale_rect_dev (check_yuv_rect_args in
-csrc/srcnn_frame_args.hpp) across the geometry of tests/test_yuv_rect_abi.py.  It is built here the way `make asan` builds
+csrc/srcnn_frame_args.hpp) across the geometry of tests/test_yuv_rect_abi.py, and holds window_tile_fits
+(csrc/srcnn_window_tile.h), the predicate that picks the fused tile kernels or the plane route for a rect's chroma, to its answers
+on tables from build_axis_table -- both routes give the same bytes, so no other test would notice it refusing everything.  It is built here the way `make asan` builds
 tests/host/host_sanitize.cpp and run as a process of its own; nothing of it is loaded into Python."""
 import os
 import shutil
