@@ -61,7 +61,10 @@ RECT_SYMBOLS = ["srcnn_rect_abi_version", "srcnn_y_path_rect_source", "srcnn_y_p
 RGB_RECT_SYMBOLS = ["srcnn_rgb_rect_abi_version", "srcnn_rgb_rect_source", "srcnn_rgb_upscale_rect_dev"]
 # one rectangle of a planar / semi-planar YUV frame (include/srcnn_amd_yuv_rect.h, listed in include/srcnn_amd_yuv_rect.abi; its own version)
 YUV_RECT_SYMBOLS = ["srcnn_yuv_rect_abi_version", "srcnn_yuv_rect_source", "srcnn_yuv_upscale_rect_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
+# one rectangle of a packed YUV frame (include/srcnn_amd_yuv_packed_rect.h, listed in include/srcnn_amd_yuv_packed_rect.abi; its own version)
+YUV_PACKED_RECT_SYMBOLS = ["srcnn_yuv_packed_rect_abi_version", "srcnn_yuv_packed_span_bytes", "srcnn_yuv_packed_rect_source",
+                           "srcnn_yuv_packed_upscale_rect_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -168,9 +171,13 @@ def lib():
             "srcnn_yuv_rect_source": (i, [C.POINTER(YuvFormat), u, u, f, i, u, u, u, u, i, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
             "srcnn_yuv_upscale_rect_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), u, u, u, u,
                                                C.POINTER(vp), C.POINTER(sz), vp]),
+            "srcnn_yuv_packed_rect_abi_version": (i, []),
+            "srcnn_yuv_packed_span_bytes": (i, [i, u, u, u, C.POINTER(u), C.POINTER(sz), C.POINTER(sz)]),
+            "srcnn_yuv_packed_rect_source": (i, [i, u, u, f, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
+            "srcnn_yuv_packed_upscale_rect_dev": (i, [i, u, u, f, i, vp, sz, u, u, u, u, vp, sz, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -753,6 +760,63 @@ def yuv_packed_upscale(frame, fmt, w, multiply=2.0, filt=SRCNNF_Bicubic, stream=
     else:
         check(lib().srcnn_stream_sync(stream))
     return dout.to_numpy(np.uint8, (dh, drb))
+
+
+def yuv_packed_span_bytes(fmt, width, x, n):
+    """(unit in pixels, byte offset, byte length) of pixels [x, x + n) of a `width`-pixel row of a packed format
+    (srcnn_yuv_packed_span_bytes; no device): x a multiple of the unit, n one or x + n == width, where the length runs to the
+    end of the tight row."""
+    unit, off, nb = C.c_uint(0), C.c_size_t(0), C.c_size_t(0)
+    check(lib().srcnn_yuv_packed_span_bytes(_yuvp_format(fmt), int(width), int(x), int(n), C.byref(unit), C.byref(off), C.byref(nb)))
+    return unit.value, off.value, nb.value
+
+
+def yuv_packed_rect_source(fmt, w, h, multiply, filt, x0, y0, rw, rh):
+    """(sx0, sy0, sw, sh): the rectangle of the w x h packed source frame, in luma pixels, that output rect
+    [x0, x0 + rw) x [y0, y0 + rh) of yuv_packed_upscale_dev(fmt, ..., multiply, filt) depends on
+    (srcnn_yuv_packed_rect_source; no device)."""
+    r = [C.c_uint(0) for _ in range(4)]
+    check(lib().srcnn_yuv_packed_rect_source(_yuvp_format(fmt), int(w), int(h), float(np.float32(multiply)), int(filt), int(x0), int(y0),
+                                             int(rw), int(rh), *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+def yuv_packed_upscale_rect_dev(fmt, w, h, multiply, filt, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, stream=None):
+    """srcnn_yuv_packed_upscale_rect_dev on device memory, as given: the arguments of yuv_packed_upscale_dev with the rect
+    (x0, y0, rw, rh) in luma output coordinates; src is the whole frame, dst the rect's row segments (or the address of the
+    rect's first byte inside a full-size frame, with that frame's pitch).  Frame arguments: a DeviceBuffer, an address, or
+    (DeviceBuffer, byte offset).  Asynchronous on `stream`; raises SrcnnError with the library's code."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_yuv_packed_upscale_rect_dev(_yuvp_format(fmt), int(w), int(h), float(np.float32(multiply)), int(filt), _addr(src),
+                                                  int(src_pitch or 0), int(x0), int(y0), int(rw), int(rh), _addr(dst), int(dst_pitch or 0),
+                                                  handle))
+
+
+def yuv_packed_upscale_rect(frame, fmt, w, rect, multiply=2.0, filt=SRCNNF_Bicubic, stream=None):
+    """Rect = (x0, y0, rw, rh) (luma output coordinates, under the format's unit rule) of yuv_packed_upscale(frame, fmt, w, ...)
+    through srcnn_yuv_packed_upscale_rect_dev: the whole packed frame in, the (rh, bytes) uint8 array of the rect's row segments
+    out, bytes as yuv_packed_span_bytes(fmt, dw, x0, rw) gives them."""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    rb, _ = yuv_packed_row_bytes(fmt, w)
+    if frame.ndim != 2 or frame.shape[1] != rb:
+        raise ValueError("a %d-pixel row of this format has %d bytes: the frame is %r" % (w, rb, frame.shape))
+    h = frame.shape[0]
+    x0, y0, rw, rh = (int(v) for v in rect)
+    din = DeviceBuffer.from_numpy(frame)
+    nb = 0
+    if rw > 0 and rh > 0:
+        dw, _dh = output_size(w, h, multiply)
+        try:
+            _unit, _off, nb = yuv_packed_span_bytes(fmt, dw, x0, rw)
+        except SrcnnError:
+            nb = 0                           # (for the call below to refuse, with its own message)
+    dout = DeviceBuffer(max(1, rh * nb))
+    yuv_packed_upscale_rect_dev(fmt, w, h, multiply, filt, din, 0, x0, y0, rw, rh, dout, 0, stream)
+    if isinstance(stream, Stream):
+        stream.sync()
+    else:
+        check(lib().srcnn_stream_sync(stream))
+    return dout.to_numpy(np.uint8, (rh, nb))
 
 
 RGB_INTERLEAVED, RGB_PLANAR = 0, 1

@@ -1,7 +1,7 @@
 // srcnn_colour_rules.h -- the bit-exact pixel rules of the colour shells, each stated once: the reference's saturation, the
 // sample codes built on it, the read of a 16-bit word, and the colour split and merge of src/libsrcnn.cpp.  The whole-frame
 // kernels (srcnn_rgb.hip, srcnn_yuv_planes.hip, srcnn_yuv_packed.hip) and the window kernels behind the rect calls
-// (srcnn_rgb_window.hip, srcnn_yuv_window.hip) call the same functions, which is why a rect holds the bytes of the frame.
+// (srcnn_rgb_window.hip, srcnn_yuv_window.hip, srcnn_yuv_packed_window.hip) call the same functions, which is why a rect holds the bytes of the frame.
 // (srcnn_kernels.hip keeps its own statements of the split and merge: its text is fingerprinted, see build.py.)
 // Every product and every sum is rounded on its own: no contraction, and the expressions are the reference's, token for
 // token.  Internal, HIP only.

@@ -1,6 +1,6 @@
 // srcnn_frame_args.hpp -- the argument half of the frame calls (srcnn_frames.cpp): what a format comes down to, and everything
 // srcnn_yuv420_upscale_dev, srcnn_yuv_upscale_dev, srcnn_yuv_packed_upscale_dev, srcnn_rgb_upscale_dev,
-// srcnn_rgb_upscale_rect_dev and srcnn_yuv_upscale_rect_dev refuse before any device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
+// srcnn_rgb_upscale_rect_dev, srcnn_yuv_upscale_rect_dev and srcnn_yuv_packed_upscale_rect_dev refuse before any device lookup.  It needs fail(), srcnn_output_size and the public headers only -- no HIP -- so tests/host/host_sanitize.cpp
 // runs the pitch and end-of-plane pointer arithmetic under the CPU sanitizers.  Internal.
 #pragma once
 #include <stddef.h>
@@ -314,6 +314,37 @@ inline int check_yuv_rect_args(const YuvGeom& g, unsigned w, unsigned h, float m
     }
     if ((rc = check_in_out_overlap(in, np, out, np))) return rc;
     return check_out_out_overlap(out, np);
+}
+
+// The unit rule of a packed span (include/srcnn_amd_yuv_packed_rect.h): pixels [x, x + n) of a `width`-pixel row, already known
+// to lie inside it.  x is a multiple of the unit; n is one, or the span ends at the row's end.  A packing unit cannot be
+// half-written without reading the destination.
+inline int check_yuv_packed_unit(const YuvPackedGeom& g, unsigned width, unsigned x, unsigned n)
+{
+    const unsigned unit = yuv_packed_unit(g.rule.kind);
+    if (x % unit || (n % unit && x + n != width))
+        return fail(SRCNN_E_ARG, "pixels [%u, %u + %u) of a %u-pixel row: the first must be a multiple of %u, and the count as well unless they end the row",
+                    x, x, n, width, unit);
+    return SRCNN_OK;
+}
+
+// srcnn_yuv_packed_upscale_rect_dev: the rules of check_yuv_packed_args with the WHOLE w x h frame as the source and rh row
+// segments of the rect's span as the destination, the rect's own rules between the scale and the planes.
+inline int check_yuv_packed_rect_args(const YuvPackedGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* src,
+                                      size_t src_pitch, unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* dst, size_t dst_pitch,
+                                      unsigned& dw, unsigned& dh, YuvPlane& in, YuvPlane& out)
+{
+    if (!src || !dst) return fail(SRCNN_E_ARG, "NULL frame");
+    if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
+    int rc;
+    if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    if ((rc = check_yuv_packed_unit(g, dw, x0, rw))) return rc;
+    size_t off = 0, n = 0;
+    yuv_packed_span(g.rule.kind, dw, x0, rw, off, n);
+    if ((rc = describe_plane(in, src, src_pitch, g.row_bytes(w), h, g.align, "input", 0))) return rc;
+    if ((rc = describe_plane(out, dst, dst_pitch, n, rh, g.align, "output", 0))) return rc;
+    return check_in_out_overlap(&in, 1, &out, 1);
 }
 
 }  // namespace srcnn

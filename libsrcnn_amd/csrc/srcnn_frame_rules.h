@@ -50,6 +50,31 @@ inline unsigned yuv_packed_chroma_cols(int kind, unsigned w)
 {
     return kind == kPk422x8 || kind == kPk422x16 || kind == kPkV210 ? (w + 1) / 2 : w;
 }
+// luma columns per chroma column: 2 for the 4:2:2 kinds, else 1
+inline unsigned yuv_packed_chroma_step(int kind) { return kind == kPk422x8 || kind == kPk422x16 || kind == kPkV210 ? 2u : 1u; }
+// the unit spans of a packed row are made of, in pixels and in bytes (srcnn_yuv_packed_span_bytes): a pixel pair of the 4:2:2
+// kinds, a pixel of the 4:4:4 kinds, a v210 group of 6
+inline unsigned yuv_packed_unit(int kind) { return kind == kPkV210 ? 6u : yuv_packed_chroma_step(kind); }
+inline unsigned yuv_packed_unit_bytes(int kind)
+{
+    switch (kind) {
+    case kPk422x8: case kPk444x8: case kPk410: return 4;
+    case kPk422x16: case kPk444x16: return 8;
+    default: return 16;
+    }
+}
+// byte offset and byte length of pixels [x, x + n) of a `width`-pixel row: x a multiple of the unit, n one or x + n == width,
+// where the length runs to the end of the tight row (the empty slots of the last unit and v210's padding groups included)
+inline void yuv_packed_span(int kind, unsigned width, unsigned x, unsigned n, size_t& offset, size_t& bytes)
+{
+    const unsigned unit = yuv_packed_unit(kind);
+    const size_t ub = yuv_packed_unit_bytes(kind);
+    offset = (size_t)(x / unit) * ub;
+    const size_t end = x + n >= width ? yuv_packed_row_bytes(kind, width) : (size_t)((x + n) / unit) * ub;
+    bytes = end - offset;
+}
+// the chroma tile width of k_yuvp_window_merge: 64, or 60 (20 groups of 3) for v210
+inline unsigned yuv_packed_tile_cols(int kind) { return kind == kPkV210 ? 60u : 64u; }
 
 // ---- RGB(A) images (include/srcnn_amd_rgb.h): what a srcnn_rgb_format comes down to (s = depth - 8) ----
 struct RgbRule {

@@ -5,6 +5,7 @@
 //   include/srcnn_amd_rgb.h          srcnn_rgb_upscale_dev           RGB(A), interleaved or planar, 8-16 bits
 //   include/srcnn_amd_rgb_rect.h     srcnn_rgb_upscale_rect_dev      one rectangle of that call's output, at the rect's cost
 //   include/srcnn_amd_yuv_rect.h     srcnn_yuv_upscale_rect_dev      one rectangle of srcnn_yuv_upscale_dev's output, likewise
+//   include/srcnn_amd_yuv_packed_rect.h  srcnn_yuv_packed_upscale_rect_dev  one rectangle of srcnn_yuv_packed_upscale_dev's, likewise
 //
 // Every call has the same skeleton: refuse what the arguments rule out before any device lookup (srcnn_frame_args.hpp), lay
 // the float planes out in ws.planes (PlaneArena), unpack the source (srcnn_yuv_planes.hip, srcnn_yuv_packed.hip,
@@ -17,6 +18,7 @@
 
 #include "../../include/srcnn_amd_rect.h"
 #include "../../include/srcnn_amd_rgb_rect.h"
+#include "../../include/srcnn_amd_yuv_packed_rect.h"
 #include "../../include/srcnn_amd_yuv_rect.h"
 #include "srcnn_frame_args.hpp"
 #include "srcnn_host.hpp"
@@ -395,6 +397,77 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
     });
 }
 
+// Luma columns [x0, x1) (under the unit rule) of rows [y0, y1) of what yuv_packed_frame writes, at the cost of the rect.  out is
+// the rect's own row segments: out.row_bytes bytes (yuv_packed_span of the rect) per row, the byte of pixel (x0, y0) first.  A
+// packed row mixes luma and chroma, so chroma and alpha are merged per band of Y', not once per rect.
+//   up-scale in both axes of the CHROMA grid, tables of at most 8 taps:  k_yuvp_window_y over the Y path's source rectangle ->
+//       per band { y_path_rect, k_yuvp_window_merge: chroma / alpha resampled from the packed source, merged, encoded, stored }
+//   everything else, and SRCNN_YUV_PACKED_RECT_UNFUSED=1:  the plane route over the window: unpack of the unit-aligned source
+//       rectangle -> per band { y_path_rect, resample_window per chroma / alpha plane, pack into the row segments }
+// Both read no byte outside the rectangle srcnn_yuv_packed_rect_source reports, and both give the bytes of yuv_packed_frame.
+int yuv_packed_rect(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane& in,
+                    const YuvPlane& out, unsigned x0, unsigned y0, unsigned x1, unsigned y1)
+{
+    Workspace& ws = *c.ws;
+    const int kind = g.rule.kind;
+    const int cfilter = chroma_filter(filter);
+    const YuvPackedChromaCols cc(kind, x0, x1);
+    const unsigned rw = x1 - x0, crw = cc.cx1 - cc.cx0;
+    const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
+    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    int rc;
+    RectSource r;
+    if ((rc = rect_source(c, filter, cfilter, w, h, dw, dh, cw, h, dcw, dh, x0, y0, x1, y1, cc.cx0, y0, cc.cx1, y1, r))) return rc;
+    unsigned char* dst = const_cast<unsigned char*>(out.lo);
+    TraceRange tr("srcnn yuv packed rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, y0, y1, dw, dh);
+
+    TableRef cv, ch_;
+    bool fused = !settings().yuv_packed_rect_unfused && dcw > cw && dh > h;
+    if (fused) {
+        if ((rc = get_table(c, cfilter, dh, h, cv))) return rc;
+        if ((rc = get_table(c, cfilter, dcw, cw, ch_))) return rc;
+        const DevAxisTable th = ch_->view(), tv = cv->view();
+        for (unsigned a = y0; a < y1 && fused; a += band)
+            fused = yuvp_window_fits(kind, TileAxis{th.h_first, th.h_taps, th.max_taps}, TileAxis{tv.h_first, tv.h_taps, tv.max_taps}, cc.cx0, crw,
+                                     a, std::min(y1, a + band) - a);
+    }
+    PlaneArena A;
+    if (fused) {
+        // [Y of the Y path's source rectangle] [Y' of one band]
+        const size_t o_y = A.take((size_t)r.yw() * r.yh()), o_band = A.take((size_t)rw * band);
+        if ((rc = ws.grow(ws.planes, A.n))) return rc;
+        float* P = ws.planes.data();
+        launch_yuvp_window_y(g.rule, in.lo, in.pitch, w, r.ylx, r.yly, r.yw(), r.yh(), P + o_y, c.s);
+        return for_each_rect_band(c, P + o_y, r.ylx, r.yly, r.yw(), r.yh(), w, h, dw, dh, filter, x0, y0, x1, y1, band, P + o_band,
+                                  [&](unsigned a, unsigned b) {
+            launch_yuvp_window_merge(g.rule, in.lo, in.pitch, w, h, P + o_band, cc.cx0, a, rw, crw, b - a, ch_->view(), cv->view(), dst, out.pitch,
+                                     a - y0, out.row_bytes, c.s);
+            return SRCNN_OK;
+        });
+    }
+    // [Y U V (A) of the unit-aligned source rectangle] [Y' U' V' (A') of one band]
+    unsigned ux, uy, uw, uh;
+    yuv_packed_source_union(kind, w, r.ylx, r.yhx, r.yly, r.yhy, r.clx, r.chx, r.cly, r.chy, ux, uy, uw, uh);
+    const unsigned cuw = g.ccols(uw), cux = ux / yuv_packed_chroma_step(kind);     // the chroma columns of that rectangle
+    const size_t o_y = A.take((size_t)uw * uh), o_u = A.take((size_t)cuw * uh), o_v = A.take((size_t)cuw * uh);
+    const size_t o_a = A.take(g.alpha ? (size_t)uw * uh : 0);
+    const size_t o_band = A.take((size_t)rw * band), o_cu = A.take((size_t)crw * band), o_cv = A.take((size_t)crw * band);
+    const size_t o_ca = A.take(g.alpha ? (size_t)rw * band : 0);
+    if ((rc = ws.grow(ws.planes, A.n))) return rc;
+    float* P = ws.planes.data();
+    size_t soff = 0, sbytes = 0;
+    yuv_packed_span(kind, w, ux, uw, soff, sbytes);
+    launch_yuvp_unpack(in.lo + (size_t)uy * in.pitch + soff, in.pitch, uw, uh, g.rule, P + o_y, P + o_u, P + o_v, g.alpha ? P + o_a : nullptr, c.s);
+    return for_each_rect_band(c, P + o_y, ux, uy, uw, uh, w, h, dw, dh, filter, x0, y0, x1, y1, band, P + o_band, [&](unsigned a, unsigned b) {
+        int rk;
+        if ((rk = resample_window(c, P + o_u, cuw, cux, uy, cw, h, dcw, dh, cfilter, cc.cx0, cc.cx1, a, b, P + o_cu))) return rk;
+        if ((rk = resample_window(c, P + o_v, cuw, cux, uy, cw, h, dcw, dh, cfilter, cc.cx0, cc.cx1, a, b, P + o_cv))) return rk;
+        if (g.alpha && (rk = resample_window(c, P + o_a, uw, ux, uy, w, h, dw, dh, cfilter, x0, x1, a, b, P + o_ca))) return rk;
+        launch_yuvp_pack(P + o_band, P + o_cu, P + o_cv, g.alpha ? P + o_ca : nullptr, rw, b - a, g.rule, dst, out.pitch, a - y0, c.s, out.row_bytes);
+        return SRCNN_OK;
+    });
+}
+
 }  // namespace
 }  // namespace srcnn
 
@@ -588,6 +661,34 @@ int srcnn_yuv_upscale_rect_dev(const srcnn_yuv_format* fmt, unsigned w, unsigned
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
     return yuv_rect(sc.c, g, w, h, dw, dh, filter, in, out, x0, y0, x0 + rw, y0 + rh);
+}
+
+// ---- one rectangle of a packed YUV frame (include/srcnn_amd_yuv_packed_rect.h) ----
+int srcnn_yuv_packed_rect_abi_version(void) { return SRCNN_AMD_YUV_PACKED_RECT_VERSION; }
+
+int srcnn_yuv_packed_span_bytes(int format, unsigned width, unsigned x, unsigned n, unsigned* unit, size_t* byte_offset, size_t* bytes)
+{
+    return yuv_packed_span_bytes(format, width, x, n, unit, byte_offset, bytes);
+}
+
+int srcnn_yuv_packed_rect_source(int format, unsigned w, unsigned h, float multiply, int filter, unsigned x0, unsigned y0, unsigned rw,
+                                 unsigned rh, unsigned* sx0, unsigned* sy0, unsigned* sw, unsigned* sh)
+{
+    return yuv_packed_rect_source(format, w, h, multiply, filter, x0, y0, rw, rh, sx0, sy0, sw, sh);
+}
+
+int srcnn_yuv_packed_upscale_rect_dev(int format, unsigned w, unsigned h, float multiply, int filter, const void* src, size_t src_pitch,
+                                      unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* dst, size_t dst_pitch, void* stream)
+{
+    YuvPackedGeom g;
+    unsigned dw = 0, dh = 0;
+    YuvPlane in, out;
+    int rc;
+    if ((rc = yuv_packed_geom(format, g))) return rc;
+    if ((rc = check_yuv_packed_rect_args(g, w, h, multiply, filter, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, dw, dh, in, out))) return rc;
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    return yuv_packed_rect(sc.c, g, w, h, dw, dh, filter, in, out, x0, y0, x0 + rw, y0 + rh);
 }
 
 }  // extern "C"

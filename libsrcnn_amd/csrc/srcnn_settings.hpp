@@ -42,7 +42,8 @@
     X(B, resample_2pass,   "SRCNN_RESAMPLE_2PASS",   0,     "0/1", "resampler: always the two generic passes (`k_resample_cols/rows`, what down-scales use); implies the unfused colour shell") \
     X(B, shell_unfused,    "SRCNN_SHELL_UNFUSED",    0,     "0/1", "colour shell as split + plane resamples + merge instead of fused into the resampler") \
     X(B, rgb_rect_unfused, "SRCNN_RGB_RECT_UNFUSED", 0,     "0/1", "RGB(A) rect call: window unpack + window plane resamples + pack for every shape instead of `k_rgb_window_merge` for up-scales") \
-    X(B, yuv_rect_unfused, "SRCNN_YUV_RECT_UNFUSED", 0,     "0/1", "YUV rect call: chroma by window unpack + window plane resamples + pack for every shape instead of `k_yuv_window_chroma` for up-scales")
+    X(B, yuv_rect_unfused, "SRCNN_YUV_RECT_UNFUSED", 0,     "0/1", "YUV rect call: chroma by window unpack + window plane resamples + pack for every shape instead of `k_yuv_window_chroma` for up-scales") \
+    X(B, yuv_packed_rect_unfused, "SRCNN_YUV_PACKED_RECT_UNFUSED", 0, "0/1", "packed YUV rect call: window unpack + window plane resamples + pack for every shape instead of `k_yuvp_window_merge` for up-scales")
 
 namespace srcnn {
 

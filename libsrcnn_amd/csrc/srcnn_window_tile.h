@@ -1,6 +1,7 @@
 // srcnn_window_tile.h -- the tile resampler under the window colour kernels of the rect calls: k_rgb_window_merge
-// (srcnn_rgb_window.hip) and k_yuv_window_chroma (srcnn_yuv_window.hip) resample NC planes of a 64 x 16 tile of the rect straight
-// from the integer source, where the plane route (srcnn_window.hip) resamples float planes of the window.
+// (srcnn_rgb_window.hip), k_yuv_window_chroma (srcnn_yuv_window.hip) and k_yuvp_window_merge (srcnn_yuv_packed_window.hip, whose
+// v210 tile is 60 columns wide) resample NC planes of a 64 x 16 tile of the rect straight from the integer source, where the plane
+// route (srcnn_window.hip) resamples float planes of the window.
 //
 // It serves up-scales in both axes with contribution tables of at most 8 taps, where the source patch of every tile fits
 // kPatchW x kPatchH: the host asks window_tile_fits, and everything else takes the plane route (srcnn_frames.cpp).  A workgroup

@@ -1,7 +1,8 @@
 // srcnn_yuv.h -- internal interface of the YUV conversion kernels: planar and semi-planar frames of every supported depth
-// (srcnn_yuv_planes.hip), their chroma over a window (srcnn_yuv_window.hip) and packed frames (srcnn_yuv_packed.hip).  The rules the launchers take are srcnn_frame_rules.h; the host
+// (srcnn_yuv_planes.hip), their chroma over a window (srcnn_yuv_window.hip), packed frames (srcnn_yuv_packed.hip) and packed frames
+// over a window (srcnn_yuv_packed_window.hip).  The rules the launchers take are srcnn_frame_rules.h; the host
 // side is srcnn_frames.cpp.  Not installed; the public surface is include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h and
-// srcnn_amd_yuv_packed.h; the rect call is include/srcnn_amd_yuv_rect.h.
+// srcnn_amd_yuv_packed.h; the rect calls are include/srcnn_amd_yuv_rect.h and include/srcnn_amd_yuv_packed_rect.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -40,7 +41,24 @@ void launch_yuvp_unpack(const unsigned char* src, size_t pitch, unsigned w, unsi
                         float* du, float* dv, float* da, hipStream_t s);
 // Tight float rows [0, rows) of sy, su, sv (sa) -> packed destination rows [row0, row0 + rows); every byte of those tight rows
 // is written once, slots without a sample as zero.  Y': (unsigned)(v * f.up); chroma and alpha: MIN(maxv), MAX(0), truncation.
+// span_bytes != 0 (the rect call): only the first span_bytes bytes of each row are written -- yuv_packed_span of the rect, which
+// for v210 stops at the rect's last group instead of the 128-byte block's end unless the rect reaches the right border.
 void launch_yuvp_pack(const float* sy, const float* su, const float* sv, const float* sa, unsigned w, unsigned rows,
-                      const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s);
+                      const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s, size_t span_bytes = 0);
+
+// ---- the window form behind the packed rect call (srcnn_yuv_packed_window.hip; include/srcnn_amd_yuv_packed_rect.h) ----
+// Luma columns [sx0, sx0 + sw) of rows [sy0, sy0 + sh) of the WHOLE w-pixel-wide packed frame src -> the tight float window y (sw
+// floats per row), (float)field * f.down: the Y half of launch_yuvp_unpack.  No byte outside yuv_packed_span of those columns
+// widened to the format's unit is read.
+void launch_yuvp_window_y(const YuvPackedRule& f, const unsigned char* src, size_t pitch, unsigned w, unsigned sx0, unsigned sy0, unsigned sw,
+                          unsigned sh, float* y, hipStream_t s);
+// One band of a rect: U', V' (and A') of chroma output columns [cx0, cx0 + ccols) and output rows [gy0, gy0 + rows) resampled from
+// the WHOLE packed w x h frame with the tables th (chroma columns) and tv (rows), an up-scale in both axes of the chroma grid,
+// merged with the band's finished Y' rows (yband: tight, rw floats per row; luma column yuv_packed_chroma_step * cx0 first) and
+// written as launch_yuvp_pack writes them into rows [row0, row0 + rows) of dst, whose first byte is the rect's first;
+// span_bytes: bytes of a row segment (yuv_packed_span of the rect).  The caller has asked yuvp_window_fits for every band.
+void launch_yuvp_window_merge(const YuvPackedRule& f, const unsigned char* src, size_t spitch, unsigned w, unsigned h, const float* yband,
+                              unsigned cx0, unsigned gy0, unsigned rw, unsigned ccols, unsigned rows, const DevAxisTable& th,
+                              const DevAxisTable& tv, unsigned char* dst, size_t dpitch, unsigned row0, size_t span_bytes, hipStream_t s);
 
 }  // namespace srcnn

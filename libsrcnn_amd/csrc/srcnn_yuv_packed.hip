@@ -8,8 +8,8 @@
 //                   U', V', A': MIN(maxv), MAX(0), truncation      the reference's macro forms on the native scale
 //                   every byte of the tight rows is written once; slots that carry no sample are written as zero
 //
-// Six memory layouts (YuvPackedKind) carry the ten public formats; byte positions, shift, maxv and scale are kernel
-// arguments.  Both kernels are memory-bound.  One lane owns one 16-byte chunk of a packed row -- 8 YUY2 pixels, 4 Y210 /
+// Six memory layouts (YuvPackedKind) carry the ten public formats, each stated once in srcnn_yuv_packed_fields.h (shared with
+// the window kernels of srcnn_yuv_packed_window.hip); byte positions, shift, maxv and scale are kernel arguments.  Both kernels are memory-bound.  One lane owns one 16-byte chunk of a packed row -- 8 YUY2 pixels, 4 Y210 /
 // VUYA / Y410 pixels, 2 Y416 pixels or one v210 group of 6 -- and consecutive lanes own consecutive chunks, so a wave reads
 // or writes 1 KiB of packed data in one instruction where base and pitch are 16-byte aligned (decided once per launch).
 // Misaligned frames and a row's last partial chunk move their dwords one by one, in pieces of the alignment the frame has
@@ -31,126 +31,13 @@
 #include "srcnn_colour_rules.h"
 #include "srcnn_pixel_io.h"
 #include "srcnn_yuv.h"
+#include "srcnn_yuv_packed_fields.h"
 
 #pragma clang fp contract(off)
 
 namespace srcnn {
 
 namespace {
-
-// samples of Y, of each chroma plane and of alpha in one 16-byte chunk
-template <int K> struct PkShape;
-template <> struct PkShape<kPk422x8>  { static constexpr unsigned NY = 8, NC = 4, NA = 0; };
-template <> struct PkShape<kPk422x16> { static constexpr unsigned NY = 4, NC = 2, NA = 0; };
-template <> struct PkShape<kPk444x8>  { static constexpr unsigned NY = 4, NC = 4, NA = 4; };
-template <> struct PkShape<kPk410>    { static constexpr unsigned NY = 4, NC = 4, NA = 4; };
-template <> struct PkShape<kPk444x16> { static constexpr unsigned NY = 2, NC = 2, NA = 2; };
-template <> struct PkShape<kPkV210>   { static constexpr unsigned NY = 6, NC = 3, NA = 0; };
-
-// how the packed side of a launch is addressed: 16-byte vectors, or pieces of 4, 2 or 1 bytes
-enum { kIoVec = 0, kIoDword = 4, kIoWord = 2, kIoByte = 1 };
-
-template <bool SAT>
-__device__ __forceinline__ unsigned to_word(float v, float scale, float maxv)
-{
-    if constexpr (SAT) return (unsigned)saturate(v, maxv);
-    else return (unsigned)(v * scale);
-}
-
-__device__ __forceinline__ unsigned load_dword(const unsigned char* p, int io)
-{
-    if (io == kIoByte) return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
-    if (io == kIoWord) {
-        const unsigned short* ps = reinterpret_cast<const unsigned short*>(p);
-        return (unsigned)ps[0] | ((unsigned)ps[1] << 16);
-    }
-    return *reinterpret_cast<const unsigned*>(p);
-}
-
-__device__ __forceinline__ void store_dword(unsigned char* p, unsigned v, int io)
-{
-    if (io == kIoByte) {
-        p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24);
-    } else if (io == kIoWord) {
-        unsigned short* ps = reinterpret_cast<unsigned short*>(p);
-        ps[0] = (unsigned short)v; ps[1] = (unsigned short)(v >> 16);
-    } else {
-        *reinterpret_cast<unsigned*>(p) = v;
-    }
-}
-
-// the four dwords of a chunk -> field values (every slot of the chunk, valid or not)
-template <int K>
-__device__ __forceinline__ void decode(const unsigned q[4], const YuvPackedRule& f, unsigned* y, unsigned* u, unsigned* v, unsigned* a)
-{
-    if constexpr (K == kPk422x8) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) {
-            y[2 * j] = (q[j] >> f.sh[0]) & 0xffu; u[j] = (q[j] >> f.sh[1]) & 0xffu;
-            y[2 * j + 1] = (q[j] >> f.sh[2]) & 0xffu; v[j] = (q[j] >> f.sh[3]) & 0xffu;
-        }
-    } else if constexpr (K == kPk422x16) {
-#pragma unroll
-        for (unsigned j = 0; j < 2; ++j) {
-            y[2 * j] = ((q[2 * j] & 0xffffu) >> f.shift) & f.mask; u[j] = ((q[2 * j] >> 16) >> f.shift) & f.mask;
-            y[2 * j + 1] = ((q[2 * j + 1] & 0xffffu) >> f.shift) & f.mask; v[j] = ((q[2 * j + 1] >> 16) >> f.shift) & f.mask;
-        }
-    } else if constexpr (K == kPk444x8) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) {
-            y[j] = (q[j] >> f.sh[0]) & 0xffu; u[j] = (q[j] >> f.sh[1]) & 0xffu;
-            v[j] = (q[j] >> f.sh[2]) & 0xffu; a[j] = (q[j] >> f.sh[3]) & 0xffu;
-        }
-    } else if constexpr (K == kPk410) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) {
-            u[j] = q[j] & 0x3ffu; y[j] = (q[j] >> 10) & 0x3ffu; v[j] = (q[j] >> 20) & 0x3ffu; a[j] = q[j] >> 30;
-        }
-    } else if constexpr (K == kPk444x16) {
-#pragma unroll
-        for (unsigned j = 0; j < 2; ++j) {
-            u[j] = q[2 * j] & 0xffffu; y[j] = q[2 * j] >> 16; v[j] = q[2 * j + 1] & 0xffffu; a[j] = q[2 * j + 1] >> 16;
-        }
-    } else {                             // v210: Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5
-        u[0] = q[0] & 0x3ffu; y[0] = (q[0] >> 10) & 0x3ffu; v[0] = (q[0] >> 20) & 0x3ffu;
-        y[1] = q[1] & 0x3ffu; u[1] = (q[1] >> 10) & 0x3ffu; y[2] = (q[1] >> 20) & 0x3ffu;
-        v[1] = q[2] & 0x3ffu; y[3] = (q[2] >> 10) & 0x3ffu; u[2] = (q[2] >> 20) & 0x3ffu;
-        y[4] = q[3] & 0x3ffu; v[2] = (q[3] >> 10) & 0x3ffu; y[5] = (q[3] >> 20) & 0x3ffu;
-    }
-}
-
-// field values (already inside their fields' ranges; zero where the slot carries no sample) -> the four dwords of a chunk
-template <int K>
-__device__ __forceinline__ void encode(const unsigned* y, const unsigned* u, const unsigned* v, const unsigned* a, const YuvPackedRule& f, unsigned q[4])
-{
-    if constexpr (K == kPk422x8) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) q[j] = (y[2 * j] << f.sh[0]) | (u[j] << f.sh[1]) | (y[2 * j + 1] << f.sh[2]) | (v[j] << f.sh[3]);
-    } else if constexpr (K == kPk422x16) {
-#pragma unroll
-        for (unsigned j = 0; j < 2; ++j) {
-            q[2 * j] = (y[2 * j] << f.shift) | (u[j] << (16 + f.shift));
-            q[2 * j + 1] = (y[2 * j + 1] << f.shift) | (v[j] << (16 + f.shift));
-        }
-    } else if constexpr (K == kPk444x8) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) q[j] = (y[j] << f.sh[0]) | (u[j] << f.sh[1]) | (v[j] << f.sh[2]) | (a[j] << f.sh[3]);
-    } else if constexpr (K == kPk410) {
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) q[j] = u[j] | (y[j] << 10) | (v[j] << 20) | (a[j] << 30);
-    } else if constexpr (K == kPk444x16) {
-#pragma unroll
-        for (unsigned j = 0; j < 2; ++j) {
-            q[2 * j] = u[j] | (y[j] << 16);
-            q[2 * j + 1] = v[j] | (a[j] << 16);
-        }
-    } else {
-        q[0] = u[0] | (y[0] << 10) | (v[0] << 20);
-        q[1] = y[1] | (u[1] << 10) | (y[2] << 20);
-        q[2] = v[1] | (y[3] << 10) | (u[2] << 20);
-        q[3] = y[4] | (v[2] << 10) | (y[5] << 20);
-    }
-}
 
 __device__ __forceinline__ unsigned valid_of(unsigned per_chunk, unsigned chunk, unsigned have)
 {
@@ -244,12 +131,6 @@ __global__ __launch_bounds__(256) void k_yuvp_pack(const float* __restrict__ sy,
     }
 }
 
-int io_of(const void* base, size_t pitch)
-{
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(base) | (uintptr_t)pitch;
-    return bits % 16 == 0 ? kIoVec : bits % 4 == 0 ? kIoDword : bits % 2 == 0 ? kIoWord : kIoByte;
-}
-
 // The row length that keeps every row start of every float plane aligned for the widest access its kind uses (float4 for 8
 // and 4 samples, float2 for 6 and 2; 3 samples go one by one).
 bool float_vec_ok(int kind, unsigned w)
@@ -288,10 +169,10 @@ void launch_yuvp_unpack(const unsigned char* src, size_t pitch, unsigned w, unsi
 }
 
 void launch_yuvp_pack(const float* sy, const float* su, const float* sv, const float* sa, unsigned w, unsigned rows,
-                      const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s)
+                      const YuvPackedRule& f, unsigned char* dst, size_t pitch, unsigned row0, hipStream_t s, size_t span_bytes)
 {
     const unsigned cw = yuv_packed_chroma_cols(f.kind, w);
-    const size_t rb = yuv_packed_row_bytes(f.kind, w);
+    const size_t rb = span_bytes ? span_bytes : yuv_packed_row_bytes(f.kind, w);   // a rect: the chunks of its span and no more
     const unsigned row_dwords = (unsigned)(rb / 4);
     const unsigned cpr = (unsigned)((rb + 15) / 16);                 // every chunk of the tight row, v210's padding groups included
     const int io = io_of(dst, pitch);
