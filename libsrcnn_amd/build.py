@@ -76,14 +76,21 @@ def kernel_source_sha(name="k_conv12_mfma"):
     (from its template header to the next banner comment) and, for the layer kernels, the constants its tile and LDS geometry
     are built from (M_* / m_* for k_conv12_mfma, C3_* for k_conv3), the LDS-DMA primitive rs_dma_dword they stage through, the
     launchers that set grid, block and dynamic LDS (launch_conv12_mfma / conv12_grid_info, launch_conv3) and the
-    host function that picks the variant (run_conv12 in srcnn_capi.cpp)."""
+    host function that picks the variant (run_conv12 in srcnn_capi.cpp).
+    Layer 3 has two fingerprints.  "k_conv3" is the template and launch_conv3, as ever.  "k_conv3_sparse" is what the strict
+    path runs by default: that kernel's section (its banner comment, C3_SPARSE, its body), the C3_* constants and rs_dma_dword
+    it shares with k_conv3, launch_layer3, which picks between the two, and launch_conv3, which launch_layer3 falls back to."""
     import hashlib
     import re
     src = open(os.path.join(CSRC, "srcnn_kernels.hip")).read()
     m = re.search(r"template <[^>]*>\s*__global__[^\n]*void %s\(" % re.escape(name), src)
+    if not m and name == "k_conv3_sparse":            # not a template: from the banner that opens its section
+        m = re.search(r"// =+\n// conv3, strict, skipping all-zero channel windows", src)
+        if m and not re.search(r"__global__[^\n]*void k_conv3_sparse\(", src[m.end():src.find("// ====", src.find("__global__", m.end()))]):
+            m = None
     if not m:
         return None
-    end = src.find("// ====", m.end())
+    end = src.find("// ====", src.find("__global__", m.end()) if name == "k_conv3_sparse" else m.end())
     parts = [src[m.start():end if end > 0 else len(src)]]
     extra = []
     if name == "k_conv12_mfma":
@@ -95,6 +102,11 @@ def kernel_source_sha(name="k_conv12_mfma"):
     elif name == "k_conv3":
         extra = [_region(src, r"constexpr int C3_TW\b", r"\ntemplate <bool STRICT"),
                  _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),
+                 _region(src, r"void launch_conv3\(", r"\n}\n")]
+    elif name == "k_conv3_sparse":
+        extra = [_region(src, r"constexpr int C3_TW\b", r"\ntemplate <bool STRICT"),
+                 _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),
+                 _region(src, r"void launch_layer3\(", r"\n}\n"),
                  _region(src, r"void launch_conv3\(", r"\n}\n")]
     if any(e is None for e in extra):
         return None                      # a region moved: better no fingerprint than a partial one

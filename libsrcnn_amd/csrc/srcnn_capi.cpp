@@ -986,7 +986,7 @@ int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_conv3(ws.c2.data(), plane, (int)dw, (int)dh, (int)ca, (int)(cb - ca), d_out, (int)r0, (int)(r1 - r0),
+        launch_layer3(ws.c2.data(), plane, (int)dw, (int)dh, (int)ca, (int)(cb - ca), d_out, (int)r0, (int)(r1 - r0),
                      c.relax(), c.s);
     }
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
@@ -1139,7 +1139,7 @@ int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned in_x
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_conv3(ws.c2.data(), plane, (int)Ww, (int)dh, (int)ca, (int)(cb - ca), ws.win.data(), (int)r0, (int)(r1 - r0), c.relax(), c.s);
+        launch_layer3(ws.c2.data(), plane, (int)Ww, (int)dh, (int)ca, (int)(cb - ca), ws.win.data(), (int)r0, (int)(r1 - r0), c.relax(), c.s);
     }
     launch_window_copy(interior, Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s);      // (outside the stage timers)
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
@@ -1792,7 +1792,7 @@ int srcnn_conv3_f32_dev(const float* d_c2, unsigned w, unsigned h, float* d_out,
     if (!ctx_for_stream(stream)) return SRCNN_E_NODEVICE;
     Call c;
     c.mode = G.mode.load();
-    launch_conv3(d_c2, (size_t)w * h, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, c.relax(), (hipStream_t)stream);
+    launch_layer3(d_c2, (size_t)w * h, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, c.relax(), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SRCNN_OK;
 }
