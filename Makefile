@@ -12,6 +12,8 @@
 #   make test       -> CPU test-suite;  make gpu-test on a gfx950 box
 #   make ubench     -> tools/ubench/bin/* (microbenchmarks; hipcc, gfx950)
 #   make asan tsan  -> the host code (table builder, drop-in control flow, frame-call argument checks, owner types, oracle) under ASan+UBSan / TSan, CPU only
+#   make pipeline-asan pipeline-tsan -> the threaded host pipeline (srcnn_capi.cpp, srcnn_pipeline.cpp: lanes, bands, bounce slots, async jobs,
+#                      frame stream and graphs, several contexts) on a fake HIP runtime under the same sanitizers, CPU only
 #   make STRICT_ONLY=1 -> the same artefacts under libsrcnn_amd/lib/strict/ with NO non-parity kernel compiled in (no FAST /
 #                      FAST_F16 / RELAXED template instance, no srcnn_fused_f16.hip); srcnn_set_mode refuses those modes
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -113,6 +115,56 @@ asan: tests/host/_build/host_asan
 tsan: tests/host/_build/host_tsan
 	TSAN_OPTIONS=halt_on_error=1 $<
 
+# The threaded host pipeline itself (srcnn_capi.cpp, srcnn_pipeline.cpp, srcnn_comm.cpp, dropin.cpp, unchanged) on a fake HIP
+# runtime and CPU launchers: tests/host/pipeline_sanitize.cpp.  Plain C++ with the ROCm clang (g++ has no _Float16 here).
+PIPE_CXX  := $(ROCM)/lib/llvm/bin/clang++
+PIPE_SRCS := tests/host/pipeline_sanitize.cpp tests/host/fake_hip.cpp tests/host/fake_kernels.cpp $(CSRC)/srcnn_capi.cpp $(CSRC)/srcnn_pipeline.cpp $(CSRC)/srcnn_comm.cpp $(CSRC)/dropin.cpp
+PIPE_FLAGS := -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Wno-unused-value -Wno-unused-result
+PIPE_SAN_asan := -fsanitize=address,undefined -fno-sanitize-recover=undefined
+PIPE_SAN_tsan := -fsanitize=thread
+# the oracle is the single-threaded reference of the comparison: ASan and UBSan check it, TSan has nothing to see in it and
+# would only slow it down (it is a third of the harness's arithmetic)
+PIPE_ORACLE_SAN_asan := $(PIPE_SAN_asan)
+PIPE_ORACLE_SAN_tsan :=
+PIPE_UNITS := pipeline_sanitize fake_hip fake_kernels srcnn_capi srcnn_pipeline srcnn_comm dropin oracle
+PIPE_DEPS := $(PIPE_SRCS) $(HDRS) oracle/srcnn_oracle.c oracle/oracle_weights.inc
+define pipe_rules
+tests/host/_build/pipe_$(1)_%.o: tests/host/%.cpp $$(PIPE_DEPS)
+	@mkdir -p tests/host/_build
+	$$(PIPE_CXX) -x c++ $$(PIPE_FLAGS) $$(PIPE_SAN_$(1)) -c $$< -o $$@
+tests/host/_build/pipe_$(1)_%.o: $$(CSRC)/%.cpp $$(PIPE_DEPS)
+	@mkdir -p tests/host/_build
+	$$(PIPE_CXX) -x c++ $$(PIPE_FLAGS) $$(PIPE_SAN_$(1)) -c $$< -o $$@
+tests/host/_build/pipe_$(1)_oracle.o: oracle/srcnn_oracle.c oracle/oracle_weights.inc
+	@mkdir -p tests/host/_build
+	$$(PIPE_CXX) -x c -std=c99 -O1 -g -ffp-contract=off -fno-omit-frame-pointer $$(PIPE_ORACLE_SAN_$(1)) -c $$< -o $$@
+# (the objects are built by a sub-make of their own, 8 at a time, whatever -j this make was given: at most 16 here)
+tests/host/_build/pipeline_$(1): $$(PIPE_DEPS)
+	@mkdir -p tests/host/_build
+	@echo 'int main() { return 0; }' | $$(PIPE_CXX) -x c++ $$(PIPE_SAN_$(1)) - -o tests/host/_build/pipe_$(1)_probe 2>/dev/null || \
+	    { echo "libpipeline-$(1): $$(PIPE_CXX) or its sanitizer runtime: No such file (tests/test_host_sanitizers.py skips on this line)" >&2; exit 1; }
+	+$$(MAKE) -j8 $$(foreach u,$$(PIPE_UNITS),tests/host/_build/pipe_$(1)_$$(u).o)
+	$$(PIPE_CXX) $$(PIPE_SAN_$(1)) $$(foreach u,$$(PIPE_UNITS),tests/host/_build/pipe_$(1)_$$(u).o) -lm -ldl -lpthread -o $$@
+endef
+$(eval $(call pipe_rules,asan))
+$(eval $(call pipe_rules,tsan))
+# every scenario as a process of its own (the library reads its switches once, at load), under both schedules of the fake
+# runtime (the two run side by side: at most ten busy threads); the goal stops at the first scenario that fails
+define pipe_run
+	@set -e; for sc in `$(1) --list`; do \
+	    env `$(1) --env $$sc` FAKE_HIP_SCHEDULE=asap $(2) $(1) $$sc & a=$$!; \
+	    env `$(1) --env $$sc` FAKE_HIP_SCHEDULE=lazy $(2) $(1) $$sc & l=$$!; \
+	    ra=0; rl=0; wait $$a || ra=$$?; wait $$l || rl=$$?; \
+	    if [ $$ra != 0 ] || [ $$rl != 0 ]; then echo "pipeline scenario $$sc FAILED (asap: $$ra, lazy: $$rl)" >&2; exit 1; fi; \
+	done
+endef
+pipeline-asan: tests/host/_build/pipeline_asan
+	$(call pipe_run,$<,ASAN_OPTIONS=detect_leaks=1:alloc_dealloc_mismatch=1:strict_string_checks=1 UBSAN_OPTIONS=print_stacktrace=1)
+	@echo "pipeline-asan: all checks passed"
+pipeline-tsan: tests/host/_build/pipeline_tsan
+	$(call pipe_run,$<,TSAN_OPTIONS=halt_on_error=1)
+	@echo "pipeline-tsan: all checks passed"
+
 install: all
 	install -d $(DESTDIR)$(PREFIX)/lib $(DESTDIR)$(PREFIX)/include
 	install -m 755 $(LIBDIR)/libsrcnn_amd.so $(DESTDIR)$(PREFIX)/lib/
@@ -149,4 +201,4 @@ uninstall:
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) oracle/_build oracle/_ref tests/host/_build tools/ubench/bin
 
-.PHONY: all oracle test gpu-test clean asan tsan ubench install install-yuv install-rgb install-rect install-yuv-packed-rect uninstall
+.PHONY: all oracle test gpu-test clean asan tsan pipeline-asan pipeline-tsan ubench install install-yuv install-rgb install-rect install-yuv-packed-rect uninstall

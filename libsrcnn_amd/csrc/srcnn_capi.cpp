@@ -528,12 +528,17 @@ void* pinned_alloc(Ctx& cx, size_t bytes)
     return p;
 }
 
-bool host_is_page_locked(const void* p)
+// The first AND the last byte: a buffer that is page-locked only in its front part (a registered block followed by pageable
+// memory, a range registered in part) must not reach the runtime's in-place pinning path whole (HostBounce in srcnn_host.hpp).
+bool host_is_page_locked(const void* p, size_t n)
 {
-    hipPointerAttribute_t a;
-    const bool yes = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return yes;
+    auto locked = [](const void* q) {
+        hipPointerAttribute_t a;
+        const bool yes = hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeHost;
+        (void)hipGetLastError();
+        return yes;
+    };
+    return locked(p) && (n <= 1 || locked(static_cast<const unsigned char*>(p) + (n - 1)));
 }
 
 namespace {
@@ -564,7 +569,7 @@ struct SlotGuard {
 int copy_h2d_any(Ctx& cx, void* d_dst, const void* h_src, size_t bytes, hipStream_t after)
 {
     if (bytes == 0) return SRCNN_OK;
-    if (pinned_by_library(h_src, bytes) || host_is_page_locked(h_src)) {
+    if (pinned_by_library(h_src, bytes) || host_is_page_locked(h_src, bytes)) {
         if (after) HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, after));
         else HIP_TRY(hipMemcpy(d_dst, h_src, bytes, hipMemcpyHostToDevice));
         return SRCNN_OK;
@@ -593,7 +598,7 @@ int copy_h2d_any(Ctx& cx, void* d_dst, const void* h_src, size_t bytes, hipStrea
 int copy_d2h_any(Ctx& cx, void* h_dst, const void* d_src, size_t bytes, hipStream_t after)
 {
     if (bytes == 0) return SRCNN_OK;
-    if (pinned_by_library(h_dst, bytes) || host_is_page_locked(h_dst)) {
+    if (pinned_by_library(h_dst, bytes) || host_is_page_locked(h_dst, bytes)) {
         if (after) HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, after));
         else HIP_TRY(hipMemcpy(h_dst, d_src, bytes, hipMemcpyDeviceToHost));
         return SRCNN_OK;

@@ -275,7 +275,7 @@ Ctx* context_at(int k);
 int get_table(Call& c, int filter, unsigned dst_len, unsigned src_len, TableRef& out);
 Workspace* workspace_for(Ctx& cx, hipStream_t s);
 bool pinned_by_library(const void* p, size_t n);   // [p, p+n) lies inside a block from srcnn_host_alloc_pinned
-bool host_is_page_locked(const void* p);           // hipHostMalloc / hipHostRegister memory (asks the runtime)
+bool host_is_page_locked(const void* p, size_t n); // [p, p+n) is hipHostMalloc / hipHostRegister memory (asks the runtime about both ends)
 // Blocking copies between device memory and ANY host memory (see HostBounce): page-locked host memory goes straight to the copy
 // engine, everything else through the context's bounce slots.  `after` (may be NULL): work already queued on that stream
 // is finished first, so the call is ordered on it like the hipMemcpyAsync it replaces.

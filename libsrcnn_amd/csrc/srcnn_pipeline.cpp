@@ -49,14 +49,6 @@ double process_cpu_seconds()
     return clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts) == 0 ? (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec : 0.0;
 }
 
-bool is_pinned(const void* p)
-{
-    hipPointerAttribute_t a;
-    const bool yes = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return yes;
-}
-
 // The caller's result buffers are fresh new[] blocks (src/libsrcnn.cpp:874-887 hands back new[] memory) whose pages fault
 // in on first touch; with 4 KB pages the fan-out memcpy is fault-bound (100 MB: 6.6-8 ms on 4-8 threads), with transparent
 // huge pages it runs at memory speed (1.5 ms) -- profiles/r03_host_out_probe.txt.  A hint only: harmless where THP is off.
@@ -789,7 +781,7 @@ int srcnn_y_upscale2x_f32_stream(const float* in, unsigned w, unsigned h, unsign
 
     // page-lock the caller's frames so the copies are truly asynchronous -- unless they already are (buffers from
     // srcnn_host_alloc_pinned / hipHostMalloc: registering a gigabyte again costs milliseconds per call); harmless if it fails
-    const bool pin_in = is_pinned(in), pin_out = is_pinned(out);
+    const bool pin_in = host_is_page_locked(in, in_b * nframes), pin_out = host_is_page_locked(out, out_b * nframes);
     const bool reg_in = !pin_in && hipHostRegister(const_cast<float*>(in), in_b * nframes, hipHostRegisterPortable) == hipSuccess;
     const bool reg_out = !pin_out && hipHostRegister(out, out_b * nframes, hipHostRegisterPortable) == hipSuccess;
     (void)hipGetLastError();

@@ -234,6 +234,19 @@ def test_nothing_outside_the_source_rectangle_is_used(srcnn, oracle_lib, name, w
     rects = edge_rects(dw, dh, rng, limit=5) + [(dw // 2, dh // 2, 1, 1), (0, 0, min(9, dw), 9), (max(0, dw - 9), dh - 9, min(9, dw), 9)]
     rects = sorted({snap(r, name, dw) for r in rects})
     assert len(rects) >= 9
+    need = 9 if w > 3 else 5
+
+    def smaller_than_the_frame(r):
+        _sx0, _sy0, sw_, sh_ = S.yuv_packed_rect_source(name, w, h, mul, filt, *r)
+        return S.yuv_packed_span_bytes(name, w, _sx0, sw_)[2] * sh_ < src.size
+
+    # The drawn edge pairs may span the frame (both lists hold 0 and the far border; a wide filter or a down-scale reaches the
+    # rest), and such a rect proves nothing here: one session seed in about 250 drew too few of the others for a case.  More rects
+    # are drawn, never fewer, until the count below can hold; the bound itself stays.
+    for _ in range(8):
+        if sum(smaller_than_the_frame(r) for r in rects) >= need:
+            break
+        rects = sorted(set(rects) | {snap(r, name, dw) for r in edge_rects(dw, dh, rng, limit=5)})
     shrunk = 0
     a_rig = Rig(S, name, src, w, mul, filt)
     for r in rects:
@@ -247,7 +260,7 @@ def test_nothing_outside_the_source_rectangle_is_used(srcnn, oracle_lib, name, w
         b = Rig(S, name, other, w, mul, filt).raw(*r)
         assert_bytes(b, a, "%s source replaced outside its rectangle, %s" % (name, name_of(r)))
         assert_bytes(a, crop(want, r, name, dw), "%s %s" % (name, name_of(r)))
-    assert shrunk >= (9 if w > 3 else 5)          # the test has teeth: most source rectangles are smaller than the frame (w = 3: in rows only)
+    assert shrunk >= need                         # the test has teeth: most source rectangles are smaller than the frame (w = 3: in rows only)
 
 
 # ---- both routes: k_yuvp_window_merge and the plane route over the window give the same bytes ----
