@@ -64,7 +64,9 @@ YUV_RECT_SYMBOLS = ["srcnn_yuv_rect_abi_version", "srcnn_yuv_rect_source", "srcn
 # one rectangle of a packed YUV frame (include/srcnn_amd_yuv_packed_rect.h, listed in include/srcnn_amd_yuv_packed_rect.abi; its own version)
 YUV_PACKED_RECT_SYMBOLS = ["srcnn_yuv_packed_rect_abi_version", "srcnn_yuv_packed_span_bytes", "srcnn_yuv_packed_rect_source",
                            "srcnn_yuv_packed_upscale_rect_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS   # everything the library exports besides the two C++ symbols
+# a list of rectangles of the Y path's output (include/srcnn_amd_rect_list.h, listed in include/srcnn_amd_rect_list.abi; its own version)
+RECT_LIST_SYMBOLS = ["srcnn_rect_list_abi_version", "srcnn_y_path_rect_list_plan", "srcnn_y_path_rect_list_f32_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -76,6 +78,17 @@ class YuvFormat(C.Structure):
 class RgbFormat(C.Structure):
     """srcnn_rgb_format (include/srcnn_amd_rgb.h)."""
     _fields_ = [("struct_size", C.c_uint), ("layout", C.c_int), ("order", C.c_int), ("alpha", C.c_int), ("depth", C.c_int)]
+
+
+class RectItem(C.Structure):
+    """srcnn_rect_item (include/srcnn_amd_rect_list.h)."""
+    _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("d_out", C.c_void_p), ("out_pitch", C.c_size_t)]
+
+
+class RectListPlan(C.Structure):
+    """srcnn_rect_list_plan (include/srcnn_amd_rect_list.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("batched_items", C.c_uint), ("single_items", C.c_uint), ("atlases", C.c_uint),
+                ("cell_samples", C.c_ulonglong), ("atlas_samples", C.c_ulonglong), ("scratch_bytes", C.c_ulonglong)]
 
 
 class SrcnnError(RuntimeError):
@@ -175,9 +188,12 @@ def lib():
             "srcnn_yuv_packed_span_bytes": (i, [i, u, u, u, C.POINTER(u), C.POINTER(sz), C.POINTER(sz)]),
             "srcnn_yuv_packed_rect_source": (i, [i, u, u, f, i, u, u, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
             "srcnn_yuv_packed_upscale_rect_dev": (i, [i, u, u, f, i, vp, sz, u, u, u, u, vp, sz, vp]),
+            "srcnn_rect_list_abi_version": (i, []),
+            "srcnn_y_path_rect_list_plan": (i, [u, u, u, u, i, vp, u, u, C.POINTER(RectListPlan)]),
+            "srcnn_y_path_rect_list_f32_dev": (i, [vp, sz, u, u, u, u, i, vp, u, u, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -458,6 +474,64 @@ def y_path_rect(plane, dw, dh, filt, x0, y0, rw, rh):
     y_path_rect_dev(din, 0, w, h, dw, dh, filt, x0, y0, rw, rh, dout, 0)
     sync()
     return dout.to_numpy(np.float32, (rh, rw))
+
+
+def rect_items(items):
+    """A ctypes array of srcnn_rect_item from (x0, y0, rw, rh[, dst[, out_pitch]]) tuples (dst: a DeviceBuffer, an address or
+    None), or `items` itself when it already is such an array.  Returns (array or None, n)."""
+    if isinstance(items, C.Array):
+        return items, len(items)
+    items = list(items)
+    if not items:
+        return None, 0
+    arr = (RectItem * len(items))()
+    for k, it in enumerate(items):
+        it = tuple(it)
+        arr[k].x0, arr[k].y0, arr[k].rw, arr[k].rh = (int(v) for v in it[:4])
+        arr[k].d_out = _addr(it[4]) if len(it) > 4 else None
+        arr[k].out_pitch = int(it[5] or 0) if len(it) > 5 else 0
+    return arr, len(items)
+
+
+def y_path_rect_list_plan(w, h, dw, dh, filt, items, n=None, item_size=None, struct_size=None):
+    """srcnn_y_path_rect_list_plan (no device): how the list call routes and packs `items` (see rect_items) at the current mode,
+    workspace limit and switches.  Returns the RectListPlan.  n / item_size / struct_size override what is passed (tests)."""
+    arr, count = rect_items(items) if items is not None else (None, 0)
+    plan = RectListPlan()
+    plan.struct_size = C.sizeof(RectListPlan) if struct_size is None else int(struct_size)
+    check(lib().srcnn_y_path_rect_list_plan(int(w), int(h), int(dw), int(dh), int(filt), C.cast(arr, C.c_void_p) if arr is not None else None,
+                                            count if n is None else int(n), C.sizeof(RectItem) if item_size is None else int(item_size),
+                                            C.byref(plan)))
+    return plan
+
+
+def y_path_rect_list_dev(src, in_pitch, w, h, dw, dh, filt, items, stream=None, n=None, item_size=None):
+    """srcnn_y_path_rect_list_f32_dev on device memory, as given: src is the whole source plane (see _addr), items the rects with
+    their destinations (see rect_items).  Asynchronous on `stream` (a Stream, a raw handle or None); the item array is read
+    before the call returns.  Raises SrcnnError with the library's code."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    arr, count = rect_items(items) if items is not None else (None, 0)
+    check(lib().srcnn_y_path_rect_list_f32_dev(_addr(src), int(in_pitch or 0), int(w), int(h), int(dw), int(dh), int(filt),
+                                               C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                               C.sizeof(RectItem) if item_size is None else int(item_size), handle))
+
+
+def y_path_rects(plane, dw, dh, filt, rects):
+    """Samples [x0, x0 + rw) x [y0, y0 + rh) of y_path(plane, dw, dh, filt) for every (x0, y0, rw, rh) of `rects`, through ONE
+    srcnn_y_path_rect_list_f32_dev call: numpy in, a list of numpy arrays out."""
+    y = _plane(plane)
+    h, w = y.shape
+    rects = [tuple(int(v) for v in r) for r in rects]
+    din = DeviceBuffer.from_numpy(y)
+    offs, total = [], 0
+    for (_, _, rw, rh) in rects:
+        offs.append(total)
+        total += (rw * rh * 4 + 15) & ~15
+    dout = DeviceBuffer(max(16, total))
+    y_path_rect_list_dev(din, 0, w, h, dw, dh, filt, [(x0, y0, rw, rh, dout.ptr + o, 0) for (x0, y0, rw, rh), o in zip(rects, offs)])
+    sync()
+    flat = dout.to_numpy(np.uint8, (max(16, total),))
+    return [flat[o:o + rw * rh * 4].view(np.float32).reshape(rh, rw).copy() for (_, _, rw, rh), o in zip(rects, offs)]
 
 
 def _stage(fn, src, out_shape, *dims):

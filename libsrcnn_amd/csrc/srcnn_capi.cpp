@@ -736,32 +736,7 @@ LaneLease::~LaneLease()
 
 namespace {
 
-// RAII bracket: records an event pair around one stage on the launch stream when profiling is on.
-struct StageTimer {
-    Ctx& cx; hipStream_t s; int stage; Event a, b; bool on;
-    Event take()
-    {
-        Event e;
-        if (!cx.event_pool.empty()) { e = std::move(cx.event_pool.back()); cx.event_pool.pop_back(); }
-        else if (hipEventCreate(e.put()) != hipSuccess) e.reset();
-        return e;
-    }
-    StageTimer(int stage_, const Call& c) : cx(*c.cx), s(c.s), stage(stage_), on(c.timing && G.profiling.load(std::memory_order_relaxed))
-    {
-        if (!on) return;
-        std::lock_guard<std::mutex> lk(cx.mu);
-        a = take(); b = take();
-        if (!a || !b) { on = false; return; }
-        (void)hipEventRecord(a.get(), s);
-    }
-    ~StageTimer()
-    {
-        if (!on) return;
-        (void)hipEventRecord(b.get(), s);
-        std::lock_guard<std::mutex> lk(cx.mu);
-        cx.spans.push_back(StageSpan{std::move(a), std::move(b), stage});
-    }
-};
+// (StageTimer, the RAII bracket of one stage on the launch stream, is srcnn_host.hpp: srcnn_rect_list_call.cpp uses it too)
 
 void drain_spans_locked(Ctx& cx)
 {
@@ -1604,7 +1579,8 @@ int srcnn_y_upscale2x_f32_band_dev(const float* d_in, unsigned w, unsigned h, un
 }
 
 // ---- one rectangle of the output (include/srcnn_amd_rect.h) --------------------------------------
-namespace {
+extern "C++" {
+namespace srcnn {
 
 // what both rect entry points refuse about the geometry, in the order the header gives
 int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
@@ -1624,7 +1600,14 @@ int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned
     return SRCNN_OK;
 }
 
-}  // namespace
+// layers 1+2 as every path of this file runs them (run_conv12), for srcnn_rect_list_call.cpp
+void run_layers12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows)
+{
+    run_conv12(c, Y, W, H, y_row_base, y_rows, C2, plane, row0, rows);
+}
+
+}  // namespace srcnn
+}  // extern "C++"
 
 int srcnn_rect_abi_version(void) { return SRCNN_AMD_RECT_VERSION; }
 

@@ -95,7 +95,17 @@ struct Scratch {            // the buffers of a Workspace: movable, so that a wo
     DevBuf<float> planes;   // colour shell: split planes / Y' / resized chroma planes
     DevBuf<float> win;      // rect call: the layer-3 result of a window (band), tight, before its interior is stored
     DevBuf<unsigned char> bytes;
-    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size() + win.size()) + bytes.size(); }
+    DevBuf<unsigned char> list;   // rect list call: the descriptor tables of a call's atlases (written in stream order)
+    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size() + win.size()) + bytes.size() + list.size(); }
+};
+// Page-locked staging of the rect list call's descriptor tables.  A call fills the next slot of the ring on the host, queues the
+// copy to Scratch::list on its stream and records the slot's event behind it; a slot is written again only after that event has
+// passed.  So a call never waits for the stream (unless four calls' copies are still queued), and calls queued back to back
+// cannot disturb each other's tables: each has a slot of its own on the host, and the device copy is rewritten in stream order.
+struct ListStaging {
+    static constexpr int kSlots = 4;
+    struct Slot { PinnedBuf pin; Event ev; bool pending = false; } slot[kSlots];
+    unsigned next = 0;
 };
 struct Workspace : Scratch {          // scratch of one stream / graph / lane; grow-only
     std::mutex mu;          // held while a call enqueues work that uses this scratch
@@ -103,13 +113,14 @@ struct Workspace : Scratch {          // scratch of one stream / graph / lane; g
     unsigned* queue = nullptr;                   // two words: the tile queue of k_conv12_mfma launches on this workspace's stream
     bool queue_dirty = false;                    // a call failed after launching: zero the counters before the next launch
     bool frozen = false;    // a captured graph has these pointers baked in: growing is an error
+    ListStaging list_stage;
     template <class T>
     int grow(DevBuf<T>& b, size_t want)          // b: one of this workspace's buffers
     {
         if (want > b.size() && frozen) return fail(SRCNN_E_ARG, "workspace of a captured graph cannot grow (%zu > %zu elements)", want, b.size());
         return b.grow(want);
     }
-    void clear() { static_cast<Scratch&>(*this) = {}; (void)hipFree(queue); queue = nullptr; }
+    void clear() { static_cast<Scratch&>(*this) = {}; list_stage = {}; (void)hipFree(queue); queue = nullptr; }
     ~Workspace() { (void)hipFree(queue); }
 };
 
@@ -263,6 +274,33 @@ private:
     bool on_;
 };
 
+// RAII bracket: records an event pair around one stage on the launch stream when profiling is on.
+struct StageTimer {
+    Ctx& cx; hipStream_t s; int stage; Event a, b; bool on;
+    Event take()
+    {
+        Event e;
+        if (!cx.event_pool.empty()) { e = std::move(cx.event_pool.back()); cx.event_pool.pop_back(); }
+        else if (hipEventCreate(e.put()) != hipSuccess) e.reset();
+        return e;
+    }
+    StageTimer(int stage_, const Call& c) : cx(*c.cx), s(c.s), stage(stage_), on(c.timing && G.profiling.load(std::memory_order_relaxed))
+    {
+        if (!on) return;
+        std::lock_guard<std::mutex> lk(cx.mu);
+        a = take(); b = take();
+        if (!a || !b) { on = false; return; }
+        (void)hipEventRecord(a.get(), s);
+    }
+    ~StageTimer()
+    {
+        if (!on) return;
+        (void)hipEventRecord(b.get(), s);
+        std::lock_guard<std::mutex> lk(cx.mu);
+        cx.spans.push_back(StageSpan{std::move(a), std::move(b), stage});
+    }
+};
+
 // ---- contexts ----
 int ensure_init();                       // at least context 0 exists (lazy: device 0, or env SRCNN_DEVICES)
 Ctx* cur_ctx();                          // the calling thread's current context, device bound; nullptr + error if init fails
@@ -316,6 +354,11 @@ int y_path_frame(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw
 int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned w, unsigned h, unsigned dw,
                 unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride,
                 bool whole_plane = true);
+// what the rect entry points refuse about the geometry, in the order include/srcnn_amd_rect.h gives, and the Y path's size limits
+int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh);
+int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned rh);
+// layers 1+2 over rows of a (W x H) plane as srcnn_capi.cpp launches them everywhere (tile queue of the workspace, clock probe)
+void run_layers12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows);
 // rows of that rect one pass produces: all of them, or the band y_path_rect cuts it into under the workspace budget
 unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1);
 // Columns [c0,c1) x rows [r0,r1) of the resampled (dw x dh) plane, tight, at the cost of that window, with the bits of

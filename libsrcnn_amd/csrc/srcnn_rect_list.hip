@@ -1,0 +1,137 @@
+// srcnn_rect_list.hip -- the kernels of the rect LIST call (include/srcnn_amd_rect_list.h): many windows of the upscaled plane
+// packed into one scratch image, the atlas, so that the unchanged layer kernels run over all of them in one launch each.
+//
+//   k_list_resample    the in-plane part of every cell, resampled from the source plane by the tile resampler
+//                      (srcnn_window_tile.h, NC = 1 with a float fetch): the bits of the plane resamplers
+//   k_list_replicate   the out-of-plane part of every cell that has one, within `depth` samples of the rect: the cell's own
+//                      sample at the clamped coordinate.  Depth 6 on the upscaled plane (what the 9x9 layer's clamp-to-edge
+//                      reads), depth 2 on the 32 layer-2 planes (layer 3 clamps the ACTIVATIONS to the edge, and layer 2 over a
+//                      replicated input is not the replicated activation).  It reads in-plane samples and writes out-of-plane
+//                      ones only, so no thread reads what another writes.
+//   k_list_scatter     every rect from the atlas result to its own d_out and pitch
+//
+// One workgroup of 256 threads takes one 64 x 16 tile of one cell.  Which cell: the descriptor table (ListCellDesc,
+// srcnn_rect_atlas.hpp) carries a prefix sum of tiles per kernel, and a workgroup finds the cell its index falls in by bisection
+// -- the same for all its threads.  The table has one closing entry with the totals; the grids are exactly those totals.
+//
+// Every index is bounded: a tile is cut to its cell part, cells lie inside the atlas (tests/host/rect_list_sanitize.cpp), the
+// source patch is clamped to the w x h plane (tile_patch), and a store to d_out stays inside the rect's rw floats per row.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "srcnn_rect_list.h"
+#include "srcnn_window_tile.h"
+
+#pragma clang fp contract(off)
+
+namespace srcnn {
+
+namespace {
+
+constexpr int kCols = kTileW / (int)kTileChunk;      // threads per tile row
+
+// the largest k < n with d[k].*START <= b (d[0].*START == 0, and b is below the total)
+template <unsigned ListCellDesc::*START>
+__device__ __forceinline__ unsigned find_cell(const ListCellDesc* __restrict__ d, unsigned n, unsigned b)
+{
+    unsigned lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if (d[mid].*START <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_list_resample(const float* __restrict__ in, size_t in_stride, unsigned w, unsigned h, const TileTables t,
+                                                       const ListCellDesc* __restrict__ d, unsigned n, float* __restrict__ atlas, unsigned atlas_w)
+{
+    __shared__ float s_patch[1][kPatchH][kPatchW];
+    __shared__ float s_mid[1][kTileH][kPatchW];
+    __shared__ int s_span[4];
+    const int tid = (int)threadIdx.x;
+    const ListCellDesc c = d[find_cell<&ListCellDesc::rs_tile0>(d, n, blockIdx.x)];
+    const unsigned tile = blockIdx.x - c.rs_tile0, tiles_x = (c.iw + kTileW - 1) / kTileW;
+    const unsigned tx = (tile % tiles_x) * kTileW, ty = (tile / tiles_x) * kTileH;       // the tile inside the in-plane part
+    if (tx >= c.iw || ty >= c.ih) return;                                                // (never: the prefix sums count these tiles)
+    const int ncol = (int)min((unsigned)kTileW, c.iw - tx), nrow = (int)min((unsigned)kTileH, c.ih - ty);
+    const unsigned gx = c.px + tx, gy = c.py + ty;                                       // the tile on the dw x dh plane
+
+    const TilePatch p = tile_patch(t, s_span, tid, gx, gy, ncol, nrow, w, h);
+    if (p.pw <= 0 || p.ph <= 0) return;                                                  // (never: window_tile_fits)
+    tile_stage<1>(s_patch, p, tid, [&](size_t sr, size_t sc, float* v) { v[0] = in[sr * in_stride + sc]; });
+    __syncthreads();
+    tile_vertical<1>(t, s_patch, s_mid, p, tid, gy, nrow);
+    __syncthreads();
+
+    const int ry = tid / kCols, cc = (tid % kCols) * (int)kTileChunk;
+    if (ry >= nrow || cc >= ncol) return;
+    const int nn = min((int)kTileChunk, ncol - cc);
+    float* out = atlas + (size_t)(c.ay + c.oy + ty + ry) * atlas_w + (c.ax + c.ox + tx + cc);
+    for (int px = 0; px < nn; ++px) {
+        float rs[1] = {0.f};
+        tile_horizontal<1>(t, s_mid, p, ry, gx + cc + px, rs);
+        out[px] = rs[0];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_list_replicate(const ListCellDesc* __restrict__ d, unsigned n, float* __restrict__ atlas, unsigned atlas_w,
+                                                        size_t plane_stride, unsigned depth)
+{
+    const int tid = (int)threadIdx.x;
+    const ListCellDesc c = d[find_cell<&ListCellDesc::rep_tile0>(d, n, blockIdx.x)];
+    const unsigned tile = blockIdx.x - c.rep_tile0, tiles_x = (c.cw + kTileW - 1) / kTileW;
+    const unsigned j = (tile / tiles_x) * kTileH + tid / kCols;                          // row of the cell
+    const unsigned i0 = (tile % tiles_x) * kTileW + (tid % kCols) * kTileChunk;          // first of this thread's columns
+    const unsigned lo = kCellMargin - depth;                                             // the ring: [lo, 6 + rw + depth) x [lo, 6 + rh + depth)
+    if (j < lo || j >= kCellMargin + c.rh + depth || j >= c.ch) return;
+    float* cell = atlas + (size_t)blockIdx.y * plane_stride + (size_t)c.ay * atlas_w + c.ax;
+    const unsigned cj = min(max(j, c.oy), c.oy + c.ih - 1);
+    const bool row_out = j != cj;
+    for (unsigned i = i0; i < i0 + kTileChunk; ++i) {
+        if (i < lo || i >= kCellMargin + c.rw + depth || i >= c.cw) continue;
+        const unsigned ci = min(max(i, c.ox), c.ox + c.iw - 1);
+        if (row_out || i != ci) cell[(size_t)j * atlas_w + i] = cell[(size_t)cj * atlas_w + ci];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_list_scatter(const ListCellDesc* __restrict__ d, unsigned n, const float* __restrict__ atlas, unsigned atlas_w)
+{
+    const int tid = (int)threadIdx.x;
+    const ListCellDesc c = d[find_cell<&ListCellDesc::sc_tile0>(d, n, blockIdx.x)];
+    const unsigned tile = blockIdx.x - c.sc_tile0, tiles_x = (c.rw + kTileW - 1) / kTileW;
+    const unsigned y = (tile / tiles_x) * kTileH + tid / kCols;                          // row of the rect
+    const unsigned x = (tile % tiles_x) * kTileW + (tid % kCols) * kTileChunk;           // first of this thread's columns
+    if (y >= c.rh || x >= c.rw) return;
+    const float* in = atlas + (size_t)(c.ay + kCellMargin + y) * atlas_w + (c.ax + kCellMargin + x);
+    float* out = reinterpret_cast<float*>((uintptr_t)c.out) + (size_t)y * c.out_stride + x;
+    const unsigned nn = min(kTileChunk, c.rw - x);
+    if (nn == kTileChunk && c.out_vec) {                     // (x is a multiple of 4: out is 16-byte aligned with d_out)
+        *reinterpret_cast<float4*>(out) = make_float4(in[0], in[1], in[2], in[3]);
+    } else {
+        for (unsigned k = 0; k < nn; ++k) out[k] = in[k];
+    }
+}
+
+}  // namespace
+
+void launch_list_resample(const float* d_in, size_t in_stride, unsigned w, unsigned h, const DevAxisTable& th, const DevAxisTable& tv,
+                          const ListCellDesc* d, unsigned ncells, const ListCellDesc& end, float* atlas, unsigned atlas_w, hipStream_t s)
+{
+    if (ncells == 0 || end.rs_tile0 == 0) return;
+    hipLaunchKernelGGL(k_list_resample, dim3(end.rs_tile0), dim3(kTileThreads), 0, s, d_in, in_stride, w, h, tile_tables(th, tv), d, ncells, atlas, atlas_w);
+}
+
+void launch_list_replicate(const ListCellDesc* d, unsigned ncells, const ListCellDesc& end, float* atlas, unsigned atlas_w, size_t plane_stride,
+                           unsigned planes, unsigned depth, hipStream_t s)
+{
+    if (ncells == 0 || end.rep_tile0 == 0 || planes == 0 || depth > kCellMargin) return;
+    hipLaunchKernelGGL(k_list_replicate, dim3(end.rep_tile0, planes), dim3(kTileThreads), 0, s, d, ncells, atlas, atlas_w, plane_stride, depth);
+}
+
+void launch_list_scatter(const ListCellDesc* d, unsigned ncells, const ListCellDesc& end, const float* atlas, unsigned atlas_w, hipStream_t s)
+{
+    if (ncells == 0 || end.sc_tile0 == 0) return;
+    hipLaunchKernelGGL(k_list_scatter, dim3(end.sc_tile0), dim3(kTileThreads), 0, s, d, ncells, atlas, atlas_w);
+}
+
+}  // namespace srcnn
