@@ -66,7 +66,9 @@ YUV_PACKED_RECT_SYMBOLS = ["srcnn_yuv_packed_rect_abi_version", "srcnn_yuv_packe
                            "srcnn_yuv_packed_upscale_rect_dev"]
 # a list of rectangles of the Y path's output (include/srcnn_amd_rect_list.h, listed in include/srcnn_amd_rect_list.abi; its own version)
 RECT_LIST_SYMBOLS = ["srcnn_rect_list_abi_version", "srcnn_y_path_rect_list_plan", "srcnn_y_path_rect_list_f32_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
+# a list of rectangles of an RGB(A) image (include/srcnn_amd_rgb_rect_list.h, listed in include/srcnn_amd_rgb_rect_list.abi; its own version)
+RGB_RECT_LIST_SYMBOLS = ["srcnn_rgb_rect_list_abi_version", "srcnn_rgb_upscale_rect_list_plan", "srcnn_rgb_upscale_rect_list_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -83,6 +85,12 @@ class RgbFormat(C.Structure):
 class RectItem(C.Structure):
     """srcnn_rect_item (include/srcnn_amd_rect_list.h)."""
     _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("d_out", C.c_void_p), ("out_pitch", C.c_size_t)]
+
+
+class RgbRectItem(C.Structure):
+    """srcnn_rgb_rect_item (include/srcnn_amd_rgb_rect_list.h)."""
+    _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("dst", C.c_void_p * 4), ("dst_pitch", C.c_size_t * 4),
+                ("dst_conv", C.c_void_p), ("dst_conv_pitch", C.c_size_t)]
 
 
 class RectListPlan(C.Structure):
@@ -191,9 +199,12 @@ def lib():
             "srcnn_rect_list_abi_version": (i, []),
             "srcnn_y_path_rect_list_plan": (i, [u, u, u, u, i, vp, u, u, C.POINTER(RectListPlan)]),
             "srcnn_y_path_rect_list_f32_dev": (i, [vp, sz, u, u, u, u, i, vp, u, u, vp]),
+            "srcnn_rgb_rect_list_abi_version": (i, []),
+            "srcnn_rgb_upscale_rect_list_plan": (i, [C.POINTER(RgbFormat), u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
+            "srcnn_rgb_upscale_rect_list_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), vp, u, u, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -1031,6 +1042,103 @@ def rgb_upscale_rect(image, rect, multiply=2.0, filt=SRCNNF_Bicubic, layout=None
     return out, (dconv.to_numpy(dt, (rh, rw)) if want_conv else None)
 
 
+def rgb_rect_items(items):
+    """A ctypes array of srcnn_rgb_rect_item from (x0, y0, rw, rh[, dst[, dst_pitch[, dst_conv[, dst_conv_pitch]]]]) tuples, or
+    `items` itself when it already is such an array.  dst: up to 4 plane arguments (each a DeviceBuffer, a (DeviceBuffer, byte
+    offset) pair or an address; interleaved uses the first only), dst_pitch: up to 4 byte counts or None (tight), dst_conv: a
+    plane argument or None.  Returns (array or None, n)."""
+    if isinstance(items, C.Array):
+        return items, len(items)
+    items = list(items)
+    if not items:
+        return None, 0
+    arr = (RgbRectItem * len(items))()
+    for k, it in enumerate(items):
+        it = tuple(it)
+        arr[k].x0, arr[k].y0, arr[k].rw, arr[k].rh = (int(v) for v in it[:4])
+        for p, plane in enumerate(it[4] if len(it) > 4 and it[4] is not None else ()):
+            arr[k].dst[p] = _addr(plane)
+        for p, pitch in enumerate(it[5] if len(it) > 5 and it[5] is not None else ()):
+            arr[k].dst_pitch[p] = int(pitch or 0)
+        arr[k].dst_conv = _addr(it[6]) if len(it) > 6 else None
+        arr[k].dst_conv_pitch = int(it[7] or 0) if len(it) > 7 else 0
+    return arr, len(items)
+
+
+def rgb_upscale_rect_list_plan(fmt, w, h, multiply, filt, items, n=None, item_size=None, struct_size=None):
+    """srcnn_rgb_upscale_rect_list_plan (no device): how the RGB(A) list call routes and packs `items` (see rgb_rect_items) at
+    the current mode, workspace limit and switches.  Returns the RectListPlan.  n / item_size / struct_size override what is
+    passed (tests)."""
+    arr, count = rgb_rect_items(items) if items is not None else (None, 0)
+    plan = RectListPlan()
+    plan.struct_size = C.sizeof(RectListPlan) if struct_size is None else int(struct_size)
+    check(lib().srcnn_rgb_upscale_rect_list_plan(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                 C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                 C.sizeof(RgbRectItem) if item_size is None else int(item_size), C.byref(plan)))
+    return plan
+
+
+def rgb_upscale_rect_list_dev(fmt, w, h, multiply, filt, src, src_pitch, items, stream=None, n=None, item_size=None):
+    """srcnn_rgb_upscale_rect_list_dev on device memory, as given: fmt, src and src_pitch as for rgb_upscale_rect_dev (the whole
+    image), items the rects with their destinations (see rgb_rect_items).  Asynchronous on `stream` (a Stream, a raw handle or
+    None); the item array is read before the call returns.  Raises SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    four = lambda xs, fill: list(xs) + [fill] * (4 - len(xs))   # noqa: E731
+    s = (vp * 4)(*[_addr(p) for p in four(src, None)]) if src is not None else None
+    sp = (sz * 4)(*four(src_pitch, 0)) if src_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    arr, count = rgb_rect_items(items) if items is not None else (None, 0)
+    check(lib().srcnn_rgb_upscale_rect_list_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                s, sp, C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                C.sizeof(RgbRectItem) if item_size is None else int(item_size), handle))
+
+
+def rgb_upscale_rects(image, rects, multiply=2.0, filt=SRCNNF_Bicubic, layout=None, order="rgb", depth=None, want_conv=False):
+    """Pixels (x0, y0, rw, rh) of rgb_upscale(image, ...) for every rect of `rects`, through ONE srcnn_rgb_upscale_rect_list_dev
+    call: numpy in, a list of numpy arrays out -- each shaped (rh, rw, c) or (c, rh, rw) like the input -- or, with want_conv,
+    a list of (out, conv) pairs."""
+    image = np.asarray(image)
+    if image.ndim != 3:
+        raise ValueError("an RGB(A) image is (h, w, c) or (c, h, w), not %r" % (image.shape,))
+    if layout is None:
+        layout = "interleaved" if image.shape[2] in (3, 4) else "planar"
+    planar = _RGB_LAYOUTS.get(layout.lower() if isinstance(layout, str) else layout, layout) == RGB_PLANAR
+    if depth is None:
+        depth = 8 if image.dtype == np.uint8 else 16
+    dt = np.uint8 if depth == 8 else np.uint16
+    image = np.ascontiguousarray(image, dt)
+    (c, h, w) = image.shape if planar else (image.shape[2], image.shape[0], image.shape[1])
+    if c not in (3, 4):
+        raise ValueError("%d channels: an RGB(A) image has 3 or 4" % c)
+    rects = [tuple(int(v) for v in r) for r in rects]
+    if not rects:
+        return []
+    fmt = rgb_format(RGB_PLANAR if planar else RGB_INTERLEAVED, order, c == 4, depth)
+    bps = np.dtype(dt).itemsize
+    din = DeviceBuffer.from_numpy(image)
+    offs, total = [], 0
+    for (_, _, rw, rh) in rects:                  # per item: the image, then the conv plane, each from a 16-byte boundary
+        o_img = total
+        total += (rw * rh * c * bps + 15) & ~15
+        o_conv = total
+        total += ((rw * rh * bps + 15) & ~15) if want_conv else 0
+        offs.append((o_img, o_conv))
+    dout = DeviceBuffer(max(16, total))
+    items = []
+    for (x0, y0, rw, rh), (o_img, o_conv) in zip(rects, offs):
+        dst = [(dout, o_img + k * rw * rh * bps) for k in range(c)] if planar else [(dout, o_img)]
+        items.append((x0, y0, rw, rh, dst, None, (dout, o_conv) if want_conv else None, 0))
+    src = [(din, k * w * h * bps) for k in range(c)] if planar else [din]
+    rgb_upscale_rect_list_dev(fmt, w, h, multiply, filt, src, None, items)
+    sync()
+    flat = dout.to_numpy(np.uint8, (max(16, total),))
+    res = []
+    for (_, _, rw, rh), (o_img, o_conv) in zip(rects, offs):
+        out = flat[o_img:o_img + rw * rh * c * bps].view(dt).reshape((c, rh, rw) if planar else (rh, rw, c)).copy()
+        res.append((out, flat[o_conv:o_conv + rw * rh * bps].view(dt).reshape(rh, rw).copy()) if want_conv else out)
+    return res
+
+
 def _one_hip_runtime():
     """torch wheels carry a HIP runtime of their own.  When torch is imported first this library binds to that copy and both
     share one runtime; the other way round the process holds two, and memory of one is unknown to the other."""
@@ -1165,6 +1273,37 @@ def rgb_upscale_rect_torch(t, rect, multiply=2.0, filt=SRCNNF_Bicubic, want_conv
     rgb_upscale_rect_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), x0, y0, rw, rh,
                          dst, dpitch, conv.data_ptr() if want_conv else None, 0, stream or None)
     return result, conv
+
+
+def rgb_upscale_rect_list_torch(t, rects, out, multiply=2.0, filt=SRCNNF_Bicubic, order="rgb", depth=None):
+    """srcnn_rgb_upscale_rect_list_dev on torch tensors that live on a GPU: repaints every (x0, y0, rw, rh) of `rects` inside
+    `out`, in place and in ONE call.  t as for rgb_upscale_torch; out is a full-size dw x dh image tensor of t's dtype, shape
+    order and memory layout (rows may be padded): the rects are written through its strides and nothing else of it is touched.
+    Queued on torch.cuda.current_stream(); returns out."""
+    W, H, Cn, bps, depth, hwc, layout, sh, sc = _rgb_torch_layout(t, depth, "rgb_upscale_rect_list_torch")
+    import torch
+    _rgb_torch_context(t)
+    dw, dh = output_size(W, H, multiply)
+    if not isinstance(out, torch.Tensor) or out.device != t.device or out.dtype != t.dtype:
+        raise ValueError("out must be a tensor of %s on %s" % (t.dtype, t.device))
+    oW, oH, oC, _, _, ohwc, olayout, osh, osc = _rgb_torch_layout(out, depth, "rgb_upscale_rect_list_torch(out)")
+    if (oW, oH, oC, ohwc, olayout) != (dw, dh, Cn, hwc, layout):
+        raise ValueError("out is %d x %d x %d (%s), the output image %d x %d x %d in the layout of t" %
+                         (oW, oH, oC, "interleaved" if olayout == RGB_INTERLEAVED else "planar", dw, dh, Cn))
+    items = []
+    for r in rects:
+        x0, y0, rw, rh = (int(v) for v in r)
+        if rw <= 0 or rh <= 0 or x0 < 0 or y0 < 0 or x0 + rw > dw or y0 + rh > dh:
+            raise ValueError("rect %r is not inside the %d x %d output" % ((x0, y0, rw, rh), dw, dh))
+        if layout == RGB_INTERLEAVED:
+            dst = [out.data_ptr() + (y0 * osh + x0 * Cn) * bps]
+        else:
+            dst = [out.data_ptr() + (k * osc + y0 * osh + x0) * bps for k in range(Cn)]
+        items.append((x0, y0, rw, rh, dst, [osh * bps] * len(dst)))
+    src = [t.data_ptr()] if layout == RGB_INTERLEAVED else [t.data_ptr() + k * sc * bps for k in range(Cn)]
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    rgb_upscale_rect_list_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), items, stream or None)
+    return out
 
 
 class PinnedArray:

@@ -271,6 +271,9 @@ int for_each_rect_band(Call& c, const float* ysrc, unsigned sx, unsigned sy, uns
 //   everything else, and SRCNN_RGB_RECT_UNFUSED=1:     the plane route over the window: unpack of the source rectangle (the
 //       union of the Y path's and the chroma taps') -> per band { y_path_rect, resample_window per chroma / alpha plane, pack }
 // Both read no sample outside the rectangle srcnn_rgb_rect_source reports, and both give the bytes of rgb_frame.
+// (Declared in srcnn_host.hpp: the single items of the RGB(A) rect list call, srcnn_rgb_rect_list_call.cpp, run it too.)
+}  // namespace
+
 int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
              const YuvPlane out[4], const YuvPlane& conv, unsigned x0, unsigned y0, unsigned x1, unsigned y1)
 {
@@ -328,6 +331,8 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
         return SRCNN_OK;
     });
 }
+
+namespace {
 
 // The luma rect [x0, x1) x [y0, y1) and the chroma samples that cover it (cr) of what yuv_frame writes, at the cost of the rect.
 // out[] are the rect's own planes (luma sample (x0, y0) and chroma sample (cr.cx0, cr.cy0) first).

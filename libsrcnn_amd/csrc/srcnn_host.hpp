@@ -365,6 +365,12 @@ unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned
 // resample_rows_range; d_in (in_stride floats per row) begins at sample (in_x0, in_y0) of the sw x sh source plane.
 int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned sw, unsigned sh,
                     unsigned dw, unsigned dh, int filter, unsigned c0, unsigned c1, unsigned r0, unsigned r1, float* d_dst);
+// The RGB(A) rect call behind srcnn_rgb_upscale_rect_dev (srcnn_frames.cpp), arguments checked (srcnn_frame_args.hpp): output
+// pixels [x0,x1) x [y0,y1) into out[] and conv, the rect's own planes; conv.lo == NULL: no truncated Y' plane.
+struct RgbRule;
+struct YuvPlane;
+int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
+             const YuvPlane out[4], const YuvPlane& conv, unsigned x0, unsigned y0, unsigned x1, unsigned y1);
 // (axis_source_span, the source span of a range of an axis without a device, is srcnn_rect_source.hpp)
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);

@@ -169,6 +169,19 @@ inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteI
     return route;
 }
 
+// The same with one more condition on a batched item: extra(rect) (the colour shell of srcnn_rgb_rect_atlas.hpp)
+template <class Extra>
+inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteInputs& in, Extra extra)
+{
+    RectListRoute route;
+    for (unsigned k = 0; k < n; ++k) {
+        if (rect_item_batched(r[k], in) && extra(r[k])) route.cells.push_back(AtlasCell{k, 0, 0, 0, r[k].rw + 2 * kCellMargin, r[k].rh + 2 * kCellMargin});
+        else route.single.push_back(k);
+    }
+    pack_rect_cells(route, in.cap_bytes);
+    return route;
+}
+
 // ---- what the kernels of srcnn_rect_list.hip read: one descriptor per cell of a pass, and one closing entry that holds the totals ----
 struct ListCellDesc {
     unsigned ax, ay, cw, ch;            // the cell in the atlas

@@ -2,7 +2,8 @@
 // packed into one scratch image, the atlas, so that the unchanged layer kernels run over all of them in one launch each.
 //
 //   k_list_resample    the in-plane part of every cell, resampled from the source plane by the tile resampler
-//                      (srcnn_window_tile.h, NC = 1 with a float fetch): the bits of the plane resamplers
+//                      (srcnn_window_tile.h, NC = 1 with a float fetch): the bits of the plane resamplers.  Its body is
+//                      list_resample_tile of srcnn_rect_list.h, which the RGB(A) list instantiates with an integer fetch
 //   k_list_replicate   the out-of-plane part of every cell that has one, within `depth` samples of the rect: the cell's own
 //                      sample at the clamped coordinate.  Depth 6 on the upscaled plane (what the 9x9 layer's clamp-to-edge
 //                      reads), depth 2 on the 32 layer-2 planes (layer 3 clamps the ACTIVATIONS to the edge, and layer 2 over a
@@ -30,48 +31,10 @@ namespace {
 
 constexpr int kCols = kTileW / (int)kTileChunk;      // threads per tile row
 
-// the largest k < n with d[k].*START <= b (d[0].*START == 0, and b is below the total)
-template <unsigned ListCellDesc::*START>
-__device__ __forceinline__ unsigned find_cell(const ListCellDesc* __restrict__ d, unsigned n, unsigned b)
-{
-    unsigned lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned mid = lo + (hi - lo) / 2;
-        if (d[mid].*START <= b) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_list_resample(const float* __restrict__ in, size_t in_stride, unsigned w, unsigned h, const TileTables t,
                                                        const ListCellDesc* __restrict__ d, unsigned n, float* __restrict__ atlas, unsigned atlas_w)
 {
-    __shared__ float s_patch[1][kPatchH][kPatchW];
-    __shared__ float s_mid[1][kTileH][kPatchW];
-    __shared__ int s_span[4];
-    const int tid = (int)threadIdx.x;
-    const ListCellDesc c = d[find_cell<&ListCellDesc::rs_tile0>(d, n, blockIdx.x)];
-    const unsigned tile = blockIdx.x - c.rs_tile0, tiles_x = (c.iw + kTileW - 1) / kTileW;
-    const unsigned tx = (tile % tiles_x) * kTileW, ty = (tile / tiles_x) * kTileH;       // the tile inside the in-plane part
-    if (tx >= c.iw || ty >= c.ih) return;                                                // (never: the prefix sums count these tiles)
-    const int ncol = (int)min((unsigned)kTileW, c.iw - tx), nrow = (int)min((unsigned)kTileH, c.ih - ty);
-    const unsigned gx = c.px + tx, gy = c.py + ty;                                       // the tile on the dw x dh plane
-
-    const TilePatch p = tile_patch(t, s_span, tid, gx, gy, ncol, nrow, w, h);
-    if (p.pw <= 0 || p.ph <= 0) return;                                                  // (never: window_tile_fits)
-    tile_stage<1>(s_patch, p, tid, [&](size_t sr, size_t sc, float* v) { v[0] = in[sr * in_stride + sc]; });
-    __syncthreads();
-    tile_vertical<1>(t, s_patch, s_mid, p, tid, gy, nrow);
-    __syncthreads();
-
-    const int ry = tid / kCols, cc = (tid % kCols) * (int)kTileChunk;
-    if (ry >= nrow || cc >= ncol) return;
-    const int nn = min((int)kTileChunk, ncol - cc);
-    float* out = atlas + (size_t)(c.ay + c.oy + ty + ry) * atlas_w + (c.ax + c.ox + tx + cc);
-    for (int px = 0; px < nn; ++px) {
-        float rs[1] = {0.f};
-        tile_horizontal<1>(t, s_mid, p, ry, gx + cc + px, rs);
-        out[px] = rs[0];
-    }
+    list_resample_tile(w, h, t, d, n, atlas, atlas_w, [&](size_t sr, size_t sc, float* v) { v[0] = in[sr * in_stride + sc]; });
 }
 
 __global__ __launch_bounds__(256) void k_list_replicate(const ListCellDesc* __restrict__ d, unsigned n, float* __restrict__ atlas, unsigned atlas_w,

@@ -33,6 +33,21 @@ void launch_rgb_window_merge(const RgbRule& f, const unsigned char* const src[4]
                              const DevAxisTable& th, const DevAxisTable& tv, unsigned char* const dst[4], const size_t dpitch[4],
                              unsigned row0, unsigned char* conv, size_t conv_pitch, hipStream_t s);
 
+// ---- the two colour kernels of the rect LIST call (srcnn_rgb_rect_list.hip; include/srcnn_amd_rgb_rect_list.h) ----
+struct ListCellDesc;         // srcnn_rect_atlas.hpp
+struct ListDstDesc;          // srcnn_rgb_rect_atlas.hpp
+// launch_list_resample (srcnn_rect_list.h) reading Y off the pitched integer plane(s) src (the WHOLE image) with the Y line of
+// launch_rgb_window_y.  th, tv: the Y tables.
+void launch_rgb_list_resample(const RgbRule& f, const unsigned char* const src[4], const size_t spitch[4], unsigned w, unsigned h,
+                              const DevAxisTable& th, const DevAxisTable& tv, const ListCellDesc* d, unsigned ncells, const ListCellDesc& end,
+                              float* atlas, unsigned atlas_w, hipStream_t s);
+// Every rect of a pass: Cb', Cr' (and A') resampled from src with the chroma tables cth (columns) and ctv (rows) as
+// launch_rgb_window_merge resamples them, merged with Y' of the atlas result and stored where dd (the device copy of the
+// pass's destination table, entry k for cell k) points.  The router has asked window_tile_fits for every rect.
+void launch_rgb_list_merge(const RgbRule& f, const unsigned char* const src[4], const size_t spitch[4], unsigned w, unsigned h,
+                           const DevAxisTable& cth, const DevAxisTable& ctv, const ListCellDesc* d, const ListDstDesc* dd, unsigned ncells,
+                           const ListCellDesc& end, const float* atlas, unsigned atlas_w, hipStream_t s);
+
 }  // namespace srcnn
 
 // One launch of the <BPS, PLANAR, D> instance of an RGB kernel template that the rule f selects (blocks of 256 threads)
