@@ -114,6 +114,9 @@ hipError_t conv12_mfma_prepare();
 void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
                         int out_rows, int relax, int num_cus, hipStream_t s, unsigned long long* clk = nullptr,
                         unsigned* queue = nullptr);
+// k_conv12_tiers: the strict LDS-DMA instance with nested zero tiers in layer 2 (SRCNN_CONV12_TIERS); same grid, block and LDS
+void launch_conv12_tiers(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
+                         int out_rows, int num_cus, hipStream_t s, unsigned long long* clk = nullptr, unsigned* queue = nullptr);
 void conv12_grid_info(int num_cus, int* blocks, int* tile_rows);
 // the same two numbers at compile time (srcnn_kernels.hip static_asserts them against M_TH / M_BPC): tile height and resident
 // workgroups per CU of the layer-1+2 kernel
