@@ -119,7 +119,7 @@ tsan: tests/host/_build/host_tsan
 # The threaded host pipeline itself (srcnn_capi.cpp, srcnn_pipeline.cpp, srcnn_comm.cpp, dropin.cpp, unchanged) on a fake HIP
 # runtime and CPU launchers: tests/host/pipeline_sanitize.cpp.  Plain C++ with the ROCm clang (g++ has no _Float16 here).
 PIPE_CXX  := $(ROCM)/lib/llvm/bin/clang++
-PIPE_SRCS := tests/host/pipeline_sanitize.cpp tests/host/fake_hip.cpp tests/host/fake_kernels.cpp tests/host/fake_kernels_tiers.cpp $(CSRC)/srcnn_capi.cpp $(CSRC)/srcnn_pipeline.cpp $(CSRC)/srcnn_comm.cpp $(CSRC)/dropin.cpp
+PIPE_SRCS := tests/host/pipeline_sanitize.cpp tests/host/fake_hip.cpp tests/host/fake_kernels.cpp $(CSRC)/srcnn_capi.cpp $(CSRC)/srcnn_pipeline.cpp $(CSRC)/srcnn_comm.cpp $(CSRC)/dropin.cpp
 PIPE_FLAGS := -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Wno-unused-value -Wno-unused-result
 PIPE_SAN_asan := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 PIPE_SAN_tsan := -fsanitize=thread
@@ -127,7 +127,7 @@ PIPE_SAN_tsan := -fsanitize=thread
 # would only slow it down (it is a third of the harness's arithmetic)
 PIPE_ORACLE_SAN_asan := $(PIPE_SAN_asan)
 PIPE_ORACLE_SAN_tsan :=
-PIPE_UNITS := pipeline_sanitize fake_hip fake_kernels fake_kernels_tiers srcnn_capi srcnn_pipeline srcnn_comm dropin oracle
+PIPE_UNITS := pipeline_sanitize fake_hip fake_kernels srcnn_capi srcnn_pipeline srcnn_comm dropin oracle
 PIPE_DEPS := $(PIPE_SRCS) $(HDRS) oracle/srcnn_oracle.c oracle/oracle_weights.inc
 define pipe_rules
 tests/host/_build/pipe_$(1)_%.o: tests/host/%.cpp $$(PIPE_DEPS)

@@ -74,21 +74,19 @@ def kernel_source_sha(name="k_conv12_mfma"):
     """sha256 of everything that decides what one launch of a kernel moves through HBM: profiles that quote a counter for
     that kernel record it, and bench.py refuses to quote a counter taken from a different text.  Covered: the kernel's body
     (from its template header to the next banner comment) and, for the layer kernels, the constants its tile and LDS geometry
-    are built from (M_* / m_* for k_conv12_mfma, C3_* for k_conv3), the LDS-DMA primitive rs_dma_dword they stage through, the
+    are built from (M_* / m_* and the zero tiers MT_* for k_conv12_mfma, C3_* for k_conv3), the LDS-DMA primitive rs_dma_dword they stage through, the
     launchers that set grid, block and dynamic LDS (launch_conv12_mfma / conv12_grid_info, launch_conv3) and the
     host function that picks the variant (run_conv12 in srcnn_capi.cpp).
     Layer 3 has two fingerprints.  "k_conv3" is the template and launch_conv3, as ever.  "k_conv3_sparse" is what the strict
     path runs by default: that kernel's section (its banner comment, C3_SPARSE, its body), the C3_* constants and rs_dma_dword
     it shares with k_conv3, launch_layer3, which picks between the two, and launch_conv3, which launch_layer3 falls back to.
-    Layers 1+2 likewise.  "k_conv12_mfma" is as ever.  "k_conv12_tiers" is what the strict path runs by default: that kernel's
-    section (banner, MT_TIER and its helpers, body), the M_* region and rs_dma_dword it shares with k_conv12_mfma,
-    launch_conv12_tiers, conv12_grid_info, run_layer12, which picks between the two, and run_conv12, the fallback."""
+    Layers 1+2 have one: every instance of k_conv12_mfma, the nested-tiers one that the strict path runs by default included,
+    is the one template, launched by the one launcher, picked by run_conv12."""
     import hashlib
     import re
     src = open(os.path.join(CSRC, "srcnn_kernels.hip")).read()
     m = re.search(r"template <[^>]*>\s*__global__[^\n]*void %s\(" % re.escape(name), src)
-    banners = {"k_conv3_sparse": r"// =+\n// conv3, strict, skipping all-zero channel windows",
-               "k_conv12_tiers": r"// =+\n// conv12, strict, nested zero tiers in layer 2"}
+    banners = {"k_conv3_sparse": r"// =+\n// conv3, strict, skipping all-zero channel windows"}
     if not m and name in banners:                     # not a template: from the banner that opens its section
         m = re.search(banners[name], src)
         if m and not re.search(r"__global__[^\n]*void %s\(" % name, src[m.end():src.find("// ====", src.find("__global__", m.end()))]):
@@ -104,14 +102,6 @@ def kernel_source_sha(name="k_conv12_mfma"):
                  _region(src, r"void conv12_grid_info\(", r"\n}\n"),
                  _region(src, r"void launch_conv12_mfma\(", r"\n}\n"),
                  _region(open(os.path.join(CSRC, "srcnn_capi.cpp")).read(), r"void run_conv12\(", r"\n}\n")]
-    elif name == "k_conv12_tiers":
-        capi = open(os.path.join(CSRC, "srcnn_capi.cpp")).read()
-        extra = [_region(src, r"constexpr int M_NW\b", r"\n// One tap-step"),
-                 _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),
-                 _region(src, r"void launch_conv12_tiers\(", r"\n}\n"),
-                 _region(src, r"void conv12_grid_info\(", r"\n}\n"),
-                 _region(capi, r"void run_layer12\(", r"\n}\n"),
-                 _region(capi, r"void run_conv12\(", r"\n}\n")]
     elif name == "k_conv3":
         extra = [_region(src, r"constexpr int C3_TW\b", r"\ntemplate <bool STRICT"),
                  _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),

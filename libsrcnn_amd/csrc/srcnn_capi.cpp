@@ -734,29 +734,15 @@ LaneLease::~LaneLease()
     cx->lane_cv.notify_one();
 }
 
-namespace {
-
-// (StageTimer, the RAII bracket of one stage on the launch stream, is srcnn_host.hpp: srcnn_rect_list_call.cpp uses it too)
-
-void drain_spans_locked(Ctx& cx)
-{
-    for (auto& sp : cx.spans) {
-        float ms = 0.f;
-        if (hipEventSynchronize(sp.b.get()) == hipSuccess && hipEventElapsedTime(&ms, sp.a.get(), sp.b.get()) == hipSuccess) {
-            cx.stage_ms[sp.stage] += ms;
-            cx.stage_n[sp.stage] += 1;
-        }
-        cx.event_pool.push_back(std::move(sp.a));
-        cx.event_pool.push_back(std::move(sp.b));
-    }
-    cx.spans.clear();
-}
-
-// Y holds rows [y_row_base, y_row_base + y_rows) of the (W x H) upscaled plane; the kernels clamp their halo
-// reads to that range as well as to the image (tile rows past the end of a band are computed but never stored).
+// Layers 1+2 as every caller runs them.  Y holds rows [y_row_base, y_row_base + y_rows) of the (W x H) upscaled plane; the
+// kernel clamps its halo reads to that range as well as to the image (tile rows past the end of a band are computed but never
+// stored).
 void run_conv12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0,
                 int rows)
 {
+    // The production strict instance chooses layer 2's body among nested zero tiers (SRCNN_CONV12_TIERS); it is the strict
+    // LDS-DMA instance with pruning on, so every other mode, SRCNN_CONV12_DMA=0 and SRCNN_CONV12_PRUNE=0 run without the tiers.
+    const bool tiers = c.relax() == 0 && settings().conv12_dma && settings().conv12_prune && settings().conv12_tiers;
     unsigned long long* clk = nullptr;
     if (G.clock_probe.load(std::memory_order_relaxed) && c.cx->clock_buf)
         clk = c.cx->clock_buf + 2 * (size_t)(c.cx->clock_n.fetch_add(1) % kClockSlots);
@@ -783,40 +769,25 @@ void run_conv12(const Call& c, const float* Y, int W, int H, int y_row_base, int
         }
         queue = c.ws->queue;
     }
-    launch_conv12_mfma(Y, W, H, y_row_base, y_rows, C2, plane, row0, rows, c.relax(), c.cx->num_cus, c.s, clk, queue);
+    launch_conv12_mfma(Y, W, H, y_row_base, y_rows, C2, plane, row0, rows, c.relax(), tiers, c.cx->num_cus, c.s, clk, queue);
 }
 
-// Layers 1+2 as every caller runs them.  The production strict kernel chooses layer 2's body among nested zero tiers
-// (k_conv12_tiers: SRCNN_CONV12_TIERS); it is the strict LDS-DMA instance with pruning on, so every other mode,
-// SRCNN_CONV12_DMA=0, SRCNN_CONV12_PRUNE=0 and SRCNN_CONV12_TIERS=0 go to run_conv12 (k_conv12_mfma), whose text is part of
-// a pinned kernel fingerprint and stays as it is.  Clock slot, foreign-capture rule and tile queue are run_conv12's, word for word.
-void run_layer12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0,
-                 int rows)
+namespace {
+
+// (StageTimer, the RAII bracket of one stage on the launch stream, is srcnn_host.hpp: srcnn_rect_list_call.cpp uses it too)
+
+void drain_spans_locked(Ctx& cx)
 {
-    if (c.relax() != 0 || !settings().conv12_dma || !settings().conv12_prune || !settings().conv12_tiers) {
-        run_conv12(c, Y, W, H, y_row_base, y_rows, C2, plane, row0, rows);
-        return;
-    }
-    unsigned long long* clk = nullptr;
-    if (G.clock_probe.load(std::memory_order_relaxed) && c.cx->clock_buf)
-        clk = c.cx->clock_buf + 2 * (size_t)(c.cx->clock_n.fetch_add(1) % kClockSlots);
-    unsigned* queue = nullptr;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool foreign_capture = c.s && c.ws && !c.ws->frozen && hipStreamIsCapturing(c.s, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive;
-    if (foreign_capture) clk = nullptr;
-    if (c.ws && settings().conv12_queue && !foreign_capture) {
-        if (c.ws->queue && c.ws->queue_dirty) {
-            if (hipMemsetAsync(c.ws->queue, 0, 2 * sizeof(unsigned), c.s) == hipSuccess) c.ws->queue_dirty = false;
-            else (void)hipGetLastError();
+    for (auto& sp : cx.spans) {
+        float ms = 0.f;
+        if (hipEventSynchronize(sp.b.get()) == hipSuccess && hipEventElapsedTime(&ms, sp.a.get(), sp.b.get()) == hipSuccess) {
+            cx.stage_ms[sp.stage] += ms;
+            cx.stage_n[sp.stage] += 1;
         }
-        if (!c.ws->queue && !c.ws->frozen) {
-            void* q = nullptr;
-            if (hipMalloc(&q, 2 * sizeof(unsigned)) == hipSuccess && hipMemsetAsync(q, 0, 2 * sizeof(unsigned), c.s) == hipSuccess) c.ws->queue = static_cast<unsigned*>(q);
-            else { (void)hipFree(q); (void)hipGetLastError(); }
-        }
-        queue = c.ws->queue;
+        cx.event_pool.push_back(std::move(sp.a));
+        cx.event_pool.push_back(std::move(sp.b));
     }
-    launch_conv12_tiers(Y, W, H, y_row_base, y_rows, C2, plane, row0, rows, c.cx->num_cus, c.s, clk, queue);
+    cx.spans.clear();
 }
 
 DevAxisTable view_of(const TableRef& t) { return t->view(); }
@@ -995,7 +966,7 @@ int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw
     const size_t plane = (size_t)dw * (cb - ca);
     {
         StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_layer12(c, ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
+        run_conv12(c, ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
@@ -1148,7 +1119,7 @@ int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned in_x
     const size_t plane = (size_t)Ww * (cb - ca);
     {
         StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_layer12(c, ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
+        run_conv12(c, ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
@@ -1633,12 +1604,6 @@ int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned
     return SRCNN_OK;
 }
 
-// layers 1+2 as every path of this file runs them (run_layer12), for srcnn_rect_list_call.cpp
-void run_layers12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows)
-{
-    run_layer12(c, Y, W, H, y_row_base, y_rows, C2, plane, row0, rows);
-}
-
 }  // namespace srcnn
 }  // extern "C++"
 
@@ -1827,7 +1792,7 @@ int srcnn_conv12_f32_dev(const float* d_y, unsigned w, unsigned h, float* d_c2, 
     c.cx = ctx_for_stream(stream);
     if (!c.cx) return SRCNN_E_NODEVICE;
     c.s = (hipStream_t)stream; c.mode = G.mode.load();
-    run_layer12(c, d_y, (int)w, (int)h, 0, (int)h, d_c2, (size_t)w * h, 0, (int)h);
+    run_conv12(c, d_y, (int)w, (int)h, 0, (int)h, d_c2, (size_t)w * h, 0, (int)h);
     HIP_TRY(hipGetLastError());
     return SRCNN_OK;
 }

@@ -357,8 +357,8 @@ int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, un
 // what the rect entry points refuse about the geometry, in the order include/srcnn_amd_rect.h gives, and the Y path's size limits
 int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned rw, unsigned rh);
 int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned rh);
-// layers 1+2 over rows of a (W x H) plane as srcnn_capi.cpp launches them everywhere (tile queue of the workspace, clock probe)
-void run_layers12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows);
+// layers 1+2 over rows of a (W x H) plane, as every path launches them (kernel instance, tile queue of the workspace, clock probe)
+void run_conv12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows);
 // rows of that rect one pass produces: all of them, or the band y_path_rect cuts it into under the workspace budget
 unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1);
 // Columns [c0,c1) x rows [r0,r1) of the resampled (dw x dh) plane, tight, at the cost of that window, with the bits of

@@ -108,15 +108,14 @@ bool launch_merge_fused(const unsigned char* rgb_src, int src_w, int src_h, int 
                         const DevAxisTable& tv, const DevAxisTable& th, hipStream_t s);
 hipError_t conv12_mfma_prepare();
 // relax: RELAX_L1 | RELAX_L2 bits (0 = strict)
+// tiers: the strict LDS-DMA instance with nested zero tiers in layer 2 (SRCNN_CONV12_TIERS); the caller has checked that the
+//        call is strict with SRCNN_CONV12_DMA and SRCNN_CONV12_PRUNE on
 // clk: NULL, or two device words that receive (shader-clock cycles, 100 MHz ticks) of workgroup 0's lifetime
 // queue: NULL (tiles dealt with a static stride), or two zeroed device words owned by the launch stream's workspace: the tile
 //        queue of the kernel (it leaves them zeroed again)
 void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
-                        int out_rows, int relax, int num_cus, hipStream_t s, unsigned long long* clk = nullptr,
+                        int out_rows, int relax, bool tiers, int num_cus, hipStream_t s, unsigned long long* clk = nullptr,
                         unsigned* queue = nullptr);
-// k_conv12_tiers: the strict LDS-DMA instance with nested zero tiers in layer 2 (SRCNN_CONV12_TIERS); same grid, block and LDS
-void launch_conv12_tiers(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
-                         int out_rows, int num_cus, hipStream_t s, unsigned long long* clk = nullptr, unsigned* queue = nullptr);
 void conv12_grid_info(int num_cus, int* blocks, int* tile_rows);
 // the same two numbers at compile time (srcnn_kernels.hip static_asserts them against M_TH / M_BPC): tile height and resident
 // workgroups per CU of the layer-1+2 kernel

@@ -618,27 +618,47 @@ static_assert(M_TH == kConv12TileRows && M_BPC == kConv12BlocksPerCU, "srcnn_ker
 // skips them in every segment where the kernel has just SEEN them all zero (below), so ANY set is correct; it only has to
 // be good.  tests/test_gpu_conv12_prune.py derives the same set from the golden weight blob.
 constexpr unsigned long long M_DEAD = 0x00044e0857e40000ull;     // 18 21 22 23 24 25 26 28 30 | 35 41 42 43 46 50
+// Nested zero tiers (SRCNN_CONV12_TIERS, the TIERS instance of the kernel): a chain of channel sets T1 = M_DEAD < T2 (< ...).
+// Layer-1 channels beyond M_DEAD are often zero TOGETHER over a 32-pixel segment (flat regions silence the edge filters at
+// once), so the largest tier whose members the wave has just seen all +-0 decides layer 2's body.  As for M_DEAD, ANY chain of
+// sets is correct; it only has to be good.  tools/conv12_zero_segments.py chooses the tiers
+// (profiles/conv12_zero_segments.txt; MT_TIER is its last lines).
+constexpr int MT_TIERS = 2;
+constexpr unsigned long long MT_TIER[MT_TIERS] = {
+    M_DEAD,                      // T1: 18 21 22 23 24 25 26 28 30 | 35 41 42 43 46 50
+    0x40174e0a77e5640aull,       // T2: T1 + 1 3 10 13 14 16 29 | 33 48 49 52 62
+};
+constexpr bool mt_nested()
+{
+    for (int t = 1; t < MT_TIERS; ++t)
+        if ((MT_TIER[t] & MT_TIER[t - 1]) != MT_TIER[t - 1] || MT_TIER[t] == MT_TIER[t - 1]) return false;
+    return MT_TIER[0] == M_DEAD;
+}
+static_assert(mt_nested(), "every tier contains the tier below, and the first is M_DEAD");
 // accumulator register r of MFMA block blk holds channel 32*blk + 8*(r/4) + 4*half + r%4: which halves of the wave hold a
-// set member there, as a lane mask
-constexpr unsigned long long m_dead_lanes(int blk, int r)
+// member of MASK there, as a lane mask
+template <unsigned long long MASK>
+constexpr unsigned long long mt_lanes(int blk, int r)
 {
     const int f = 32 * blk + 8 * (r >> 2) + (r & 3);
-    return ((M_DEAD >> f) & 1 ? 0x00000000ffffffffull : 0ull) | ((M_DEAD >> (f + 4)) & 1 ? 0xffffffff00000000ull : 0ull);
+    return ((MASK >> f) & 1 ? 0x00000000ffffffffull : 0ull) | ((MASK >> (f + 4)) & 1 ? 0xffffffff00000000ull : 0ull);
 }
-constexpr int m_live_count(int blk)
+template <unsigned long long MASK>
+constexpr int mt_live_count(int blk)
 {
     int n = 0;
-    for (int f = 0; f < 32; ++f) n += !((M_DEAD >> (32 * blk + f)) & 1);
+    for (int f = 0; f < 32; ++f) n += !((MASK >> (32 * blk + f)) & 1);
     return n;
 }
-constexpr int m_live_nth(int blk, int n)            // the n-th live channel of the block, counted within the block
+template <unsigned long long MASK>
+constexpr int mt_live_nth(int blk, int n)           // the n-th channel of the block that is not in MASK, counted within the block
 {
     for (int f = 0; f < 32; ++f)
-        if (!((M_DEAD >> (32 * blk + f)) & 1) && n-- == 0) return f;
+        if (!((MASK >> (32 * blk + f)) & 1) && n-- == 0) return f;
     return -1;
 }
-static_assert(m_live_nth(0, 0) == 0 && m_live_nth(0, 1) == 1, "the pruned body starts, like the full one, with the pair (0, 1)");
-static_assert(m_live_count(0) >= 4 && m_live_count(1) >= 4, "two pairs per block are fetched ahead");
+static_assert(mt_live_nth<M_DEAD>(0, 0) == 0 && mt_live_nth<M_DEAD>(0, 1) == 1, "the M_DEAD body starts, like the full one, with the pair (0, 1)");
+static_assert(mt_live_count<MT_TIER[MT_TIERS - 1]>(0) >= 4 && mt_live_count<MT_TIER[MT_TIERS - 1]>(1) >= 4, "two pairs per block are fetched ahead");
 template <int N, class F>
 __device__ __forceinline__ void m_static_for(F&& f)       // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
 {
@@ -655,12 +675,20 @@ constexpr int m_lds_floats(bool ld) { return M_W1 + M_W2 + M_B1 + M_B2 + m_ybufs
 // RELAX: bit 0 = layer 1, bit 1 = layer 2 evaluated as FMA chains on the matrix pipe (C = acc: one rounding per tap instead of
 // the reference's two).  0 = STRICT (production, bit-exact), 3 = SRCNN_MODE_FAST; 1 and 2 exist for the per-layer error
 // matrix (profiles/r04_error_matrix.txt) and the SRCNN_MODE_RELAXED experiments.
-template <int RELAX, bool LD>
+// TIERS: strict layer 2 chooses per 32-channel block and 32-pixel segment between the full body and one body per tier of
+// MT_TIER (production: <0, true, true>, SRCNN_CONV12_TIERS, profiles/conv12_tiers_ab.txt).  TIERS = false chooses between
+// the full body and the body without M_DEAD's members, and only where `prune` is set (SRCNN_CONV12_PRUNE); the TIERS instance
+// is launched only with pruning on and does not read `prune`.  Either way the decision is what measured fastest on this
+// kernel (docs/HISTORY.md 4.1): one wave-uniform branch per block between fully unrolled, re-paired bodies, no per-channel
+// control flow.  Everything else -- tile, tile queue and quarter tiles, staging, barriers, LDS layout, layer 1, the
+// epilogue's stores -- is the same code for every instance.
+template <int RELAX, bool LD, bool TIERS = false>
 __global__ __launch_bounds__(64 * M_NW, 4) void k_conv12_mfma(
     const float* __restrict__ Y, int W, int H, int y_row_base, int y_rows,
     float* __restrict__ C2, size_t plane_stride, int out_row0, int out_rows, int tiles_x, int ntiles,
     unsigned long long* __restrict__ clk, unsigned* __restrict__ queue, int prune)
 {
+    static_assert(!TIERS || (RELAX == 0 && LD), "the tiers exist for the strict LDS-DMA instance only");
     constexpr int NW = M_NW, NT = 64 * NW, TH = M_TH, YT = M_YT;
     // clk != NULL (srcnn_debug_clock_probe): workgroup 0 -- resident from the first round to the last -- stamps the shader
     // clock counter and the constant 100 MHz counter when it starts and when it ends: their ratio is the clock this launch ran at
@@ -837,15 +865,36 @@ __global__ __launch_bounds__(64 * M_NW, 4) void k_conv12_mfma(
             f32x16 acc2 = {};
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                unsigned long long live = 0;       // lanes that hold a nonzero value of a near-dead channel (M_DEAD) of this block
+                // Is any member of T1 = M_DEAD, or (TIERS) of T2 but not T1, nonzero on one of the 32 pixels?  Magnitude bits: -0 is
+                // zero, NaN, Inf and denormals are not.  The two forms of the test differ, and each instance keeps the
+                // instructions it was measured with; making them one is a separate, measured change.
+                // TIERS = false: one compare + ballot per register that holds a member of M_DEAD (6 + 5 vector instructions).
+                // TIERS: a register holds channel f in the lower half of the wave and f + 4 in the upper, so of a set it may hold a
+                // member in both halves, the lower or the upper.  The bit patterns of the registers of each kind are ORed together
+                // per lane (v_or3_b32 takes three at a time), the half that applies is selected, and ONE mask + compare + ballot
+                // per set decides: 10 vector instructions in block 0 and 9 in block 1 for both sets.  A compare per register of
+                // T2 (11 and 9) measured the same (profiles/conv12_tiers_ab.txt).
+                static_assert(MT_TIERS == 2, "the test below and the choice of body are written out for two tiers");
+                constexpr unsigned long long D1 = MT_TIER[0], D2 = MT_TIER[MT_TIERS - 1] & ~MT_TIER[0];
+                constexpr unsigned long long LO = 0x00000000ffffffffull, HI = 0xffffffff00000000ull;
+                [[maybe_unused]] unsigned long long live = 0;   // TIERS = false: lanes that hold a nonzero value of a member of M_DEAD of this block
+                [[maybe_unused]] unsigned any1 = 0, lo1 = 0, hi1 = 0, any2 = 0, lo2 = 0, hi2 = 0;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float v = fmaxf(acc[16 * blk + r] + B1s[half * 32 + 16 * blk + r], 0.f);
                     const int f = 8 * (r >> 2) + (r & 3);                  // + 4*half : channel within the block
                     myC1[(f + 4 * half) * 32 + col] = v;
-                    // magnitude bits: -0 is zero, NaN and denormals are not.  One compare per register that holds a set member.
-                    if (STRICT2 && m_dead_lanes(blk, r))
-                        live |= __builtin_amdgcn_ballot_w64((__float_as_uint(v) & 0x7fffffffu) != 0u) & m_dead_lanes(blk, r);
+                    const unsigned u = __float_as_uint(v);
+                    if constexpr (TIERS) {
+                        if (mt_lanes<D1>(blk, r) == (LO | HI)) any1 |= u; else if (mt_lanes<D1>(blk, r) == LO) lo1 |= u; else if (mt_lanes<D1>(blk, r) == HI) hi1 |= u;
+                        if (mt_lanes<D2>(blk, r) == (LO | HI)) any2 |= u; else if (mt_lanes<D2>(blk, r) == LO) lo2 |= u; else if (mt_lanes<D2>(blk, r) == HI) hi2 |= u;
+                    } else if (STRICT2 && mt_lanes<D1>(blk, r))
+                        live |= __builtin_amdgcn_ballot_w64((u & 0x7fffffffu) != 0u) & mt_lanes<D1>(blk, r);
+                }
+                [[maybe_unused]] bool live1 = true, live2 = true;   // TIERS: a member of T1 / of T2 but not T1 is nonzero on one of the 32 pixels
+                if constexpr (TIERS) {
+                    live1 = __builtin_amdgcn_ballot_w64(((any1 | (half ? hi1 : lo1)) & 0x7fffffffu) != 0u) != 0;
+                    live2 = __builtin_amdgcn_ballot_w64(((any2 | (half ? hi2 : lo2)) & 0x7fffffffu) != 0u) != 0;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -856,52 +905,63 @@ __global__ __launch_bounds__(64 * M_NW, 4) void k_conv12_mfma(
                 const float* w2p = W2s + blk * 16 * 64;
                 float a1 = w2p[lane], b1 = myC1[lane];
                 float a2 = w2p[64 + lane], b2 = myC1[64 + lane];
+                // The body without the members of MT_TIER[T], taken where every one of them is +-0 on all 32 pixels of this
+                // segment (one wave-uniform decision per block, from the values just written to the slab): only the block's
+                // remaining channels are multiplied and added, in ascending order, paired consecutively (fa < fb; lanes 0-31
+                // carry fa, lanes 32-63 fb) -- for M_DEAD 12 + 13 MFMAs and 392 packed adds instead of 32 and 512.
+                // Why that is exact: a skipped channel's activations are +-0, so its products with the (finite) layer-2
+                // weights are +-0, and x + (+-0) = x for every nonzero or NaN x.  For x = +-0 only the SIGN of a zero
+                // accumulator can differ from the reference's, and the bias add of the epilogue erases that: no
+                // layer-2 bias is +-0 (the smallest magnitude is 0.051; tests/test_gpu_conv12_prune.py and
+                // tests/test_conv12_tiers_cpu.py check both facts).  The argument asks nothing else of a skipped channel.
+                // Layer 1 is untouched: a channel is not known to be zero before it has been computed.
+                // W2s is flat [f][m] and the slab flat [f][px], so weight and activation of a pair are read at the
+                // same per-lane offset ((half ? fb : fa) * 32 + col), written relative to `lane` so that consecutive
+                // channels are an immediate offset from the full body's two addresses.  An odd count leaves the second
+                // block of the block's last MFMA unused (it repeats fa) and unadded.
+                // The two pairs fetched above are the full body's: the M_DEAD bodies start with the same pairs (block 1's
+                // second pair apart), so on content that takes no larger tier the first MFMA's operands are on their way
+                // while the scalar unit decides.
+                auto tier_body = [&](auto BLK, auto T) {
+                    constexpr int B = decltype(BLK)::value;
+                    constexpr unsigned long long MASK = MT_TIER[decltype(T)::value];
+                    constexpr int NL = mt_live_count<MASK>(B), NP = (NL + 1) / 2;
+                    auto off = [&](auto P) {
+                        constexpr int p = decltype(P)::value, fa = mt_live_nth<MASK>(B, 2 * p), fb = 2 * p + 1 < NL ? mt_live_nth<MASK>(B, 2 * p + 1) : fa;
+                        return lane + 32 * fa + (lane & 32) * (fb - fa - 1);
+                    };
+                    const int o0 = off(std::integral_constant<int, 0>{}), o1 = off(std::integral_constant<int, 1>{});
+                    a1 = w2p[o0]; b1 = myC1[o0];
+                    a2 = w2p[o1]; b2 = myC1[o1];
+                    m_static_for<NP>([&](auto P) {
+                        constexpr int p = decltype(P)::value;
+                        f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
+                        PIN(d);
+                        a1 = a2; b1 = b2;
+                        if constexpr (p + 2 < NP) { const int o = off(std::integral_constant<int, p + 2>{}); a2 = w2p[o]; b2 = myC1[o]; }
+                        if constexpr (B == 0 && p == 0) acc2 = __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+                        else
+                        acc2 += __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+                        if constexpr (2 * p + 1 < NL)
+                        acc2 += __builtin_shufflevector(d, d, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
+                        PIN(acc2);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                };
+                const std::integral_constant<int, 0> I0{};
+                const std::integral_constant<int, 1> I1{};
                 if constexpr (!STRICT2) {
                     // FAST: the slab/weight layout (lanes 0-31 channel f, lanes 32-63 channel f+1) is exactly the
                     // K=2 operand layout of the single-block MFMA, so the pair is one chained FMA update of acc2.
 #pragma unroll
                     for (int fp = 0; fp < 16; ++fp)
                         acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w2p[fp * 64 + lane], myC1[fp * 64 + lane], acc2, 0, 0, 0);
-                } else if (prune && live == 0) {
-                    // PRUNED block: every near-dead channel of the block is +-0 on all 32 pixels of this segment (one
-                    // wave-uniform decision per block, taken from the values just written to the slab), so only the block's
-                    // live channels are multiplied and added: in ascending order, paired consecutively (fa < fb; lanes 0-31
-                    // carry fa, lanes 32-63 fb) -- 12 + 13 MFMAs and 392 packed adds instead of 32 and 512.
-                    // Why that is exact: a skipped channel's activations are +-0, so its products with the (finite) layer-2
-                    // weights are +-0, and x + (+-0) = x for every nonzero or NaN x.  For x = +-0 only the SIGN of a zero
-                    // accumulator can differ from the reference's, and the bias add of the epilogue erases that: no
-                    // layer-2 bias is +-0 (the smallest magnitude is 0.051; tests/test_gpu_conv12_prune.py checks it).
-                    // Layer 1 is untouched: a channel is not known to be dead before it has been computed.
-                    // W2s is flat [f][m] and the slab flat [f][px], so weight and activation of a pair are read at the
-                    // same per-lane offset ((half ? fb : fa) * 32 + col), written relative to `lane` so that consecutive
-                    // channels (all pairs but four) are an immediate offset from the full body's two addresses.  An odd
-                    // live count leaves the second block of the block's last MFMA unused (it repeats fa) and unadded.
-                    auto pruned = [&](auto BLK) {
-                        constexpr int B = decltype(BLK)::value, NL = m_live_count(B), NP = (NL + 1) / 2;
-                        auto off = [&](auto P) {
-                            constexpr int p = decltype(P)::value, fa = m_live_nth(B, 2 * p), fb = 2 * p + 1 < NL ? m_live_nth(B, 2 * p + 1) : fa;
-                            return lane + 32 * fa + (lane & 32) * (fb - fa - 1);
-                        };
-                        const int o0 = off(std::integral_constant<int, 0>{}), o1 = off(std::integral_constant<int, 1>{});
-                        a1 = w2p[o0]; b1 = myC1[o0];
-                        a2 = w2p[o1]; b2 = myC1[o1];
-                        m_static_for<NP>([&](auto P) {
-                            constexpr int p = decltype(P)::value;
-                            f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
-                            PIN(d);
-                            a1 = a2; b1 = b2;
-                            if constexpr (p + 2 < NP) { const int o = off(std::integral_constant<int, p + 2>{}); a2 = w2p[o]; b2 = myC1[o]; }
-                            if constexpr (B == 0 && p == 0) acc2 = __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                            else
-                            acc2 += __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                            if constexpr (2 * p + 1 < NL)
-                            acc2 += __builtin_shufflevector(d, d, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
-                            PIN(acc2);
-                            __builtin_amdgcn_sched_barrier(0);
-                        });
-                    };
-                    if (blk == 0) pruned(std::integral_constant<int, 0>{}); else pruned(std::integral_constant<int, 1>{});
+                } else if (TIERS && !live1 && !live2) {
+                    if (blk == 0) tier_body(I0, I1); else tier_body(I1, I1);         // every member of T2 is +-0
+                } else if (TIERS ? !live1 : prune && live == 0) {
+                    if (blk == 0) tier_body(I0, I0); else tier_body(I1, I0);         // every member of T1 = M_DEAD is
                 } else {
+                    // the full body
 #pragma unroll
                     for (int fp = 0; fp < 16; ++fp) {
                         f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
@@ -937,294 +997,6 @@ __global__ __launch_bounds__(64 * M_NW, 4) void k_conv12_mfma(
     }
     if (dyn && tid == 0) {
         // every draw of this workgroup has returned (its value went through the mailbox); the last one out resets the queue
-        if (atomicAdd(queue + 1, 1u) == gridDim.x - 1) { queue[0] = 0u; queue[1] = 0u; }
-    }
-    if (clk && blockIdx.x == 0) {
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            clk[0] = __builtin_amdgcn_s_memtime() - clk_c0;
-            clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-        }
-    }
-}
-
-// =============================================================================================
-// conv12, strict, nested zero tiers in layer 2: the production layer-1+2 kernel (SRCNN_CONV12_TIERS, default 1).
-// It is k_conv12_mfma<0, true> with `prune` on -- same tile, tile queue and quarter tiles, same LDS-DMA staging, barriers and
-// LDS layout (m_lds_floats), same layer 1, same epilogue stores, written out for that one instance -- with one difference:
-// where that kernel chooses per 32-channel block between the full layer-2 body and the body without M_DEAD's members, this
-// one chooses between the full body and one body per TIER, a chain of nested channel sets T1 = M_DEAD < T2 (< ...).  Layer-1
-// channels beyond M_DEAD are often zero TOGETHER over a 32-pixel segment (flat regions silence the edge filters at once), so
-// the largest tier whose members the wave has just seen all +-0 decides the body.  The decision stays what measured fastest
-// on this kernel (docs/HISTORY.md 4.1): one wave-uniform branch per block between fully unrolled, re-paired bodies, no
-// per-channel control flow.  Exactness is k_conv12_mfma's argument for M_DEAD (see `pruned` there), which asks nothing of a
-// skipped channel but that its 32 activations are +-0, the layer-2 weights finite and no layer-2 bias +-0
-// (tests/test_conv12_tiers_cpu.py checks the last two); so ANY chain of sets is correct, it only has to be good.
-// tools/conv12_zero_segments.py chooses the tiers (profiles/conv12_zero_segments.txt; MT_TIER below is its last lines).
-//
-// Why a kernel of its own: k_conv12_mfma's text, the M_* region, launch_conv12_mfma and run_conv12 are pinned by
-// build.kernel_source_sha("k_conv12_mfma"), whose value tests/test_rect_abi.py asserts.  k_conv12_mfma stays the fallback
-// (non-parity tiers, SRCNN_CONV12_DMA=0, SRCNN_CONV12_PRUNE=0, SRCNN_CONV12_TIERS=0).  The price: the staging, the tile
-// queue and layer 1 exist twice and must be kept in step by hand (tests/test_gpu_conv12_tiers.py runs both kernels on the same
-// planes against the oracle).  When the pin next moves, fold this back: MT_TIER replaces M_DEAD, `tier_body` replaces `pruned`.
-// Its loads and stores are k_conv12_mfma<0, true>'s, one for one.  Fingerprint: kernel_source_sha("k_conv12_tiers").
-// =============================================================================================
-constexpr int MT_TIERS = 2;
-constexpr unsigned long long MT_TIER[MT_TIERS] = {
-    M_DEAD,                      // T1: 18 21 22 23 24 25 26 28 30 | 35 41 42 43 46 50
-    0x40174e0a77e5640aull,       // T2: T1 + 1 3 10 13 14 16 29 | 33 48 49 52 62
-};
-constexpr bool mt_nested()
-{
-    for (int t = 1; t < MT_TIERS; ++t)
-        if ((MT_TIER[t] & MT_TIER[t - 1]) != MT_TIER[t - 1] || MT_TIER[t] == MT_TIER[t - 1]) return false;
-    return MT_TIER[0] == M_DEAD;
-}
-static_assert(mt_nested(), "every tier contains the tier below, and the first is M_DEAD");
-// as m_dead_lanes, for any channel set: which halves of the wave hold a member of MASK in accumulator register r of block blk
-template <unsigned long long MASK>
-constexpr unsigned long long mt_lanes(int blk, int r)
-{
-    const int f = 32 * blk + 8 * (r >> 2) + (r & 3);
-    return ((MASK >> f) & 1 ? 0x00000000ffffffffull : 0ull) | ((MASK >> (f + 4)) & 1 ? 0xffffffff00000000ull : 0ull);
-}
-template <unsigned long long MASK>
-constexpr int mt_live_count(int blk)
-{
-    int n = 0;
-    for (int f = 0; f < 32; ++f) n += !((MASK >> (32 * blk + f)) & 1);
-    return n;
-}
-template <unsigned long long MASK>
-constexpr int mt_live_nth(int blk, int n)           // the n-th channel of the block that is not in MASK, counted within the block
-{
-    for (int f = 0; f < 32; ++f)
-        if (!((MASK >> (32 * blk + f)) & 1) && n-- == 0) return f;
-    return -1;
-}
-static_assert(mt_live_count<MT_TIER[MT_TIERS - 1]>(0) >= 4 && mt_live_count<MT_TIER[MT_TIERS - 1]>(1) >= 4, "two pairs per block are fetched ahead");
-
-__global__ __launch_bounds__(64 * M_NW, 4) void k_conv12_tiers(
-    const float* __restrict__ Y, int W, int H, int y_row_base, int y_rows,
-    float* __restrict__ C2, size_t plane_stride, int out_row0, int out_rows, int tiles_x, int ntiles,
-    unsigned long long* __restrict__ clk, unsigned* __restrict__ queue)
-{
-    constexpr int NW = M_NW, NT = 64 * NW, TH = M_TH, YT = M_YT;
-    // clk != NULL (srcnn_debug_clock_probe): as in k_conv12_mfma
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (clk && blockIdx.x == 0) { clk_c0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* W1s = lds;                    // [tap][lane]: lane = channel
-    float* W2s = W1s + M_W1;             // [f/2][lane]: lanes 0-31 -> w2[m=lane][f], 32-63 -> w2[m=lane-32][f+1]
-    float* B1s = W2s + M_W2;             // [half][reg] layer-1 bias in accumulator layout
-    float* B2s = B1s + M_B1;             // [half][reg] layer-2 bias in accumulator layout
-    float* Yt  = B2s + M_B2;             // [2][YT]
-    float* C1s = Yt + m_ybufs(true) * YT;
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, col = lane & 31;
-
-    // the block's weight image by LDS-DMA: all 15 pieces per thread in flight at once, landed before the first tile's barrier
-    const int wave_e0w = __builtin_amdgcn_readfirstlane(tid & ~63);
-#pragma unroll
-    for (int i = 0; i < (M_W1 + NT - 1) / NT; ++i) {
-        const int e = tid + i * NT;
-        if (e < M_W1) rs_dma_dword(&cW.w1t[0][0] + e, W1s + i * NT + wave_e0w);
-    }
-#pragma unroll
-    for (int i = 0; i < (M_W2 + NT - 1) / NT; ++i) {
-        const int e = tid + i * NT;
-        if (e < M_W2) { const int fp = e >> 6, l = e & 63; rs_dma_dword(&cW.w2[l & 31][2 * fp + (l >> 5)], W2s + i * NT + wave_e0w); }
-    }
-    if (tid < 64) {
-        const int hf = tid >> 5, r = tid & 31;
-        rs_dma_dword(&cW.b1[32 * (r >> 4) + 8 * ((r & 15) >> 2) + 4 * hf + (r & 3)], B1s);
-    }
-    if (tid < 32) {
-        const int hf = tid >> 4, r = tid & 15;
-        rs_dma_dword(&cW.b2[8 * (r >> 2) + 4 * hf + (r & 3)], B2s);
-    }
-    float* myC1 = C1s + wv * M_C1;
-    const f32x32 zero32 = {};
-
-    // persistent grid; whole tiles for the rounds the grid fills, quarter tiles for the last round (k_conv12_mfma)
-    const int full = (ntiles / (int)gridDim.x) * (int)gridDim.x;
-    const int nitems = full + 4 * (ntiles - full);
-    constexpr int NPRE = (YT + NT - 1) / NT;
-    auto tile_of = [&](int item, int& s0, int& s1) {
-        int tile = item; s0 = 0; s1 = 4;
-        if (item >= full) { const int i = item - full; tile = full + (i >> 2); s0 = i & 3; s1 = s0 + 1; }
-        return tile;
-    };
-    const int wave_e0 = wave_e0w;         // first element of this wave's 64 (an SGPR: the DMA's LDS base must be uniform)
-    auto request = [&](int item, float* buf) {
-        int q0, q1;
-        const int tile = tile_of(item, q0, q1);
-        const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-        const int tx0 = txi * M_TW, ty0 = out_row0 + tyi * TH;
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int e = tid + i * NT;
-            if (e < YT) {
-                const int r = e / M_LW, c = e - r * M_LW;
-                const int gy = clampi(clampi(ty0 + r - 4, 0, H - 1), y_row_base, y_row_base + y_rows - 1), gx = clampi(tx0 + c - 4, 0, W - 1);
-                rs_dma_dword(Y + (size_t)(gy - y_row_base) * W + gx, buf + i * NT + wave_e0);
-            }
-        }
-    };
-    // static stride (queue == NULL) or the tile queue with its two-slot LDS mailbox (k_conv12_mfma)
-    int* qslot = reinterpret_cast<int*>(C1s + NW * M_C1);
-    const bool dyn = queue != nullptr;
-    int it = 0;
-    int item = blockIdx.x;
-    if (item < nitems) request(item, Yt);
-    if (dyn && tid == 0 && item < nitems) qslot[0] = (int)gridDim.x + (int)atomicAdd(queue, 1u);
-    for (; item < nitems; ++it) {
-        int s0, s1;
-        const int tile = tile_of(item, s0, s1);
-        const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
-        const int tx0 = txi * M_TW, ty0 = out_row0 + tyi * TH;
-        int next_item = item + (int)gridDim.x;
-        int drawn = 0x7fffffff;
-        const float* Ytc = Yt + (it & 1) * YT;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the item's tile has landed
-        __syncthreads();                                    // ... everybody's has; the previous item is finished everywhere
-        if (dyn) next_item = __builtin_amdgcn_readfirstlane(qslot[it & 1]);
-        if (next_item < nitems) request(next_item, Yt + ((it + 1) & 1) * YT);
-        if (dyn && tid == 0 && next_item < nitems) drawn = (int)gridDim.x + (int)atomicAdd(queue, 1u);     // the item after next
-
-#pragma unroll 1
-        for (int s = s0; s < s1; ++s) {
-            const int sg = wv * 4 + s;
-            const int trow = sg >> 1, seg = sg & 1;
-            const float* yrow = Ytc + trow * M_LW + seg * 32 + col;
-
-            // ---- layer 1: 81 taps, one MFMA (products) + 16 packed adds each (k_conv12_mfma's strict form) ----
-            f32x32 acc = zero32;
-            {
-                float a1 = W1s[lane], b1 = yrow[0];
-                float a2 = W1s[64 + lane], b2 = yrow[1];
-#pragma unroll
-                for (int t = 0; t < 81; ++t) {
-                    f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
-                    PIN(d);
-                    a1 = a2; b1 = b2;
-                    if (t + 2 < 81) {
-                        a2 = W1s[(t + 2) * 64 + lane];
-                        b2 = yrow[((t + 2) / 9) * M_LW + ((t + 2) % 9)];
-                    }
-                    if (t == 0) acc = d; else acc += d;
-                    PIN(acc);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            // ---- bias + ReLU, then layer 2, one MFMA block (32 channels) at a time through the wave's LDS slab [f][px] ----
-            f32x16 acc2 = {};
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                // Is any member of T1, or of T2 but not T1, nonzero on one of the 32 pixels?  (Magnitude bits: -0 is zero, NaN, Inf
-                // and denormals are not.)  A register holds channel f in the lower half of the wave and f + 4 in the upper, so of a
-                // set it may hold a member in both halves, the lower or the upper.  The bit patterns of the registers of each
-                // kind are ORed together per lane (v_or3_b32 takes three at a time), the half that applies is selected, and
-                // ONE mask + compare + ballot per set decides: 10 vector instructions in block 0 and 9 in block 1 for both sets,
-                // where k_conv12_mfma's one compare per register costs 6 and 5 for M_DEAD alone.  A compare per register of T2
-                // (11 and 9) measured the same (profiles/conv12_tiers_ab.txt).
-                constexpr unsigned long long D1 = MT_TIER[0], D2 = MT_TIER[MT_TIERS - 1] & ~MT_TIER[0];
-                constexpr unsigned long long LO = 0x00000000ffffffffull, HI = 0xffffffff00000000ull;
-                unsigned any1 = 0, lo1 = 0, hi1 = 0, any2 = 0, lo2 = 0, hi2 = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = fmaxf(acc[16 * blk + r] + B1s[half * 32 + 16 * blk + r], 0.f);
-                    const int f = 8 * (r >> 2) + (r & 3);                  // + 4*half : channel within the block
-                    myC1[(f + 4 * half) * 32 + col] = v;
-                    const unsigned u = __float_as_uint(v);
-                    if (mt_lanes<D1>(blk, r) == (LO | HI)) any1 |= u; else if (mt_lanes<D1>(blk, r) == LO) lo1 |= u; else if (mt_lanes<D1>(blk, r) == HI) hi1 |= u;
-                    if (mt_lanes<D2>(blk, r) == (LO | HI)) any2 |= u; else if (mt_lanes<D2>(blk, r) == LO) lo2 |= u; else if (mt_lanes<D2>(blk, r) == HI) hi2 |= u;
-                }
-                const bool live1 = __builtin_amdgcn_ballot_w64(((any1 | (half ? hi1 : lo1)) & 0x7fffffffu) != 0u) != 0;
-                const bool live2 = __builtin_amdgcn_ballot_w64(((any2 | (half ? hi2 : lo2)) & 0x7fffffffu) != 0u) != 0;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-                // The first two pairs of the full body are fetched before the body is chosen, as in k_conv12_mfma: the T1 bodies
-                // start with the same pairs (block 1's second pair apart), so on content that takes no tier beyond T1 the first
-                // MFMA's operands are on their way while the scalar unit decides.
-                const float* w2p = W2s + blk * 16 * 64;
-                float a1 = w2p[lane], b1 = myC1[lane];
-                float a2 = w2p[64 + lane], b2 = myC1[64 + lane];
-                // The body without the members of MT_TIER[T]: the block's remaining channels in ascending order, paired
-                // consecutively (fa < fb; lanes 0-31 carry fa, lanes 32-63 fb).  W2s is flat [f][m] and the slab flat [f][px], so
-                // weight and activation of a pair are read at the same per-lane offset ((half ? fb : fa) * 32 + col).  An odd
-                // count leaves the second block of the last MFMA unused (it repeats fa) and unadded.
-                auto tier_body = [&](auto BLK, auto T) {
-                    constexpr int B = decltype(BLK)::value;
-                    constexpr unsigned long long MASK = MT_TIER[decltype(T)::value];
-                    constexpr int NL = mt_live_count<MASK>(B), NP = (NL + 1) / 2;
-                    auto off = [&](auto P) {
-                        constexpr int p = decltype(P)::value, fa = mt_live_nth<MASK>(B, 2 * p), fb = 2 * p + 1 < NL ? mt_live_nth<MASK>(B, 2 * p + 1) : fa;
-                        return lane + 32 * fa + (lane & 32) * (fb - fa - 1);
-                    };
-                    const int o0 = off(std::integral_constant<int, 0>{}), o1 = off(std::integral_constant<int, 1>{});
-                    a1 = w2p[o0]; b1 = myC1[o0];
-                    a2 = w2p[o1]; b2 = myC1[o1];
-                    m_static_for<NP>([&](auto P) {
-                        constexpr int p = decltype(P)::value;
-                        f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
-                        PIN(d);
-                        a1 = a2; b1 = b2;
-                        if constexpr (p + 2 < NP) { const int o = off(std::integral_constant<int, p + 2>{}); a2 = w2p[o]; b2 = myC1[o]; }
-                        if constexpr (B == 0 && p == 0) acc2 = __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                        else
-                        acc2 += __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                        if constexpr (2 * p + 1 < NL)
-                        acc2 += __builtin_shufflevector(d, d, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
-                        PIN(acc2);
-                        __builtin_amdgcn_sched_barrier(0);
-                    });
-                };
-                const std::integral_constant<int, 0> B0{};
-                const std::integral_constant<int, 1> B1{};
-                if (!live1 && !live2) {
-                    // every member of T2 is +-0 on all 32 pixels of this segment
-                    if (blk == 0) tier_body(B0, std::integral_constant<int, 1>{}); else tier_body(B1, std::integral_constant<int, 1>{});
-                } else if (!live1) {
-                    // every member of T1 = M_DEAD is: k_conv12_mfma's pruned body
-                    if (blk == 0) tier_body(B0, std::integral_constant<int, 0>{}); else tier_body(B1, std::integral_constant<int, 0>{});
-                } else {
-                    // the full body: 16 MFMAs per block, each = channels (f, f+1) x 32 outputs x 32 pixels
-#pragma unroll
-                    for (int fp = 0; fp < 16; ++fp) {
-                        f32x32 d = __builtin_amdgcn_mfma_f32_32x32x1f32(a1, b1, zero32, 0, 0, 0);
-                        PIN(d);
-                        a1 = a2; b1 = b2;
-                        if (fp + 2 < 16) { a2 = w2p[(fp + 2) * 64 + lane]; b2 = myC1[(fp + 2) * 64 + lane]; }
-                        if (blk == 0 && fp == 0) acc2 = __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                        else
-                        acc2 += __builtin_shufflevector(d, d, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-                        acc2 += __builtin_shufflevector(d, d, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
-                        PIN(acc2);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();     // slab is rewritten by the next block / segment
-            }
-
-            // ---- bias + ReLU + store: reg r -> output m = 8*(r/4) + 4*half + r%4, pixel col ----
-            const int row = ty0 + trow, x = tx0 + seg * 32 + col;
-            if (row < out_row0 + out_rows && row < H && x < W) {
-                float* dst = C2 + (size_t)(row - out_row0) * W + x + (size_t)(4 * half) * plane_stride;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = 8 * (r >> 2) + (r & 3);      // + 4*half
-                    dst[(size_t)m * plane_stride] = fmaxf(acc2[r] + B2s[half * 16 + r], 0.f);
-                }
-            }
-        }
-        if (dyn && tid == 0) qslot[(it + 1) & 1] = drawn;        // read by everybody after the next item's barrier
-        item = next_item;
-    }
-    if (dyn && tid == 0) {
-        // every draw of this workgroup has returned; the last one out resets the queue
         if (atomicAdd(queue + 1, 1u) == gridDim.x - 1) { queue[0] = 0u; queue[1] = 0u; }
     }
     if (clk && blockIdx.x == 0) {
@@ -2058,10 +1830,10 @@ bool launch_merge_fused(const unsigned char* rgb_src, int src_w, int src_h, int 
 
 // The layer-1+2 kernel's instantiations: RELAX 0 = strict (production, and its no-DMA fallback), 3 = SRCNN_MODE_FAST, 1 / 2 = the
 // single-layer relaxations of SRCNN_MODE_RELAXED (the instrument behind profiles/r04_error_matrix.txt).
-template <int RELAX, bool LD>
+template <int RELAX, bool LD, bool TIERS = false>
 static hipError_t prep_one()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_mfma<RELAX, LD>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_mfma<RELAX, LD, TIERS>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * m_lds_floats(LD)));
 }
 
@@ -2070,8 +1842,7 @@ hipError_t conv12_mfma_prepare()
     hipError_t e;
     if ((e = prep_one<0, true>()) != hipSuccess) return e;
     if ((e = prep_one<0, false>()) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv12_tiers), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(sizeof(float) * m_lds_floats(true)))) != hipSuccess) return e;
+    if ((e = prep_one<0, true, true>()) != hipSuccess) return e;
 #ifndef SRCNN_STRICT_ONLY            // make STRICT_ONLY=1: no instance of a non-parity kernel is compiled
     if ((e = prep_one<1, true>()) != hipSuccess) return e;
     if ((e = prep_one<2, true>()) != hipSuccess) return e;
@@ -2089,7 +1860,7 @@ void conv12_grid_info(int num_cus, int* blocks, int* tile_rows)
 }
 
 void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
-                        int out_rows, int relax, int num_cus, hipStream_t s, unsigned long long* clk, unsigned* queue)
+                        int out_rows, int relax, bool tiers, int num_cus, hipStream_t s, unsigned long long* clk, unsigned* queue)
 {
     if (out_rows <= 0) return;
     const int prune = settings().conv12_prune ? 1 : 0;       // strict layer 2 may skip near-dead channels (M_DEAD)
@@ -2099,35 +1870,22 @@ void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows
     // such a "last round" out in quarter tiles, so up to four blocks share a tile instead of three quarters of the chip idling
     const int cap = M_BPC * num_cus;
     const int grid = ntiles >= cap ? cap : (settings().conv12_spread ? std::min(4 * ntiles, cap) : ntiles);
-#define CONV12_GO(R, LD) hipLaunchKernelGGL((k_conv12_mfma<R, LD>), dim3(grid), dim3(64 * M_NW), sizeof(float) * m_lds_floats(LD), s, Y, W, H, \
-                                           y_row_base, y_rows, C2, plane_stride, out_row0, out_rows, tiles_x, ntiles, clk, LD ? queue : nullptr, prune)
+#define CONV12_GO(R, LD, T) hipLaunchKernelGGL((k_conv12_mfma<R, LD, T>), dim3(grid), dim3(64 * M_NW), sizeof(float) * m_lds_floats(LD), s, Y, W, H, \
+                                              y_row_base, y_rows, C2, plane_stride, out_row0, out_rows, tiles_x, ntiles, clk, LD ? queue : nullptr, prune)
+    // tiers: the caller (run_conv12) has checked that the call is strict, with LDS-DMA staging and pruning on
+    if (tiers) { CONV12_GO(0, true, true); return; }
 #ifdef SRCNN_STRICT_ONLY
     (void)relax;                     // srcnn_set_mode refuses every other mode in this build
-    if (settings().conv12_dma) CONV12_GO(0, true); else CONV12_GO(0, false);
+    if (settings().conv12_dma) CONV12_GO(0, true, false); else CONV12_GO(0, false, false);
 #else
     switch (relax & 3) {
-    case 0: if (settings().conv12_dma) CONV12_GO(0, true); else CONV12_GO(0, false); break;
-    case 1: CONV12_GO(1, true); break;
-    case 2: CONV12_GO(2, true); break;
-    default: CONV12_GO(3, true); break;
+    case 0: if (settings().conv12_dma) CONV12_GO(0, true, false); else CONV12_GO(0, false, false); break;
+    case 1: CONV12_GO(1, true, false); break;
+    case 2: CONV12_GO(2, true, false); break;
+    default: CONV12_GO(3, true, false); break;
     }
 #endif
 #undef CONV12_GO
-}
-
-// The strict layer-1+2 kernel with nested zero tiers (k_conv12_tiers): launch_conv12_mfma's grid, block and dynamic LDS for
-// its strict LDS-DMA instance.  The caller (run_layer12) has checked that this kernel covers the call.
-void launch_conv12_tiers(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
-                         int out_rows, int num_cus, hipStream_t s, unsigned long long* clk, unsigned* queue)
-{
-    if (out_rows <= 0) return;
-    const int tiles_x = (int)cdiv(W, M_TW), tiles_y = (int)cdiv(out_rows, M_TH);
-    const int ntiles = tiles_x * tiles_y;
-    int cap = 0;
-    conv12_grid_info(num_cus, &cap, nullptr);
-    const int grid = ntiles >= cap ? cap : (settings().conv12_spread ? std::min(4 * ntiles, cap) : ntiles);
-    hipLaunchKernelGGL(k_conv12_tiers, dim3(grid), dim3(64 * M_NW), sizeof(float) * m_lds_floats(true), s, Y, W, H, y_row_base, y_rows,
-                       C2, plane_stride, out_row0, out_rows, tiles_x, ntiles, clk, queue);
 }
 
 void launch_conv3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out,

@@ -71,7 +71,7 @@ int rect_list_pass(Call& c, const float* d_in, size_t in_stride, unsigned w, uns
     }
     {
         StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_layers12(c, ws.up.data(), (int)W, (int)H, 0, (int)H, ws.c2.data(), plane, 0, (int)H);
+        run_conv12(c, ws.up.data(), (int)W, (int)H, 0, (int)H, ws.c2.data(), plane, 0, (int)H);
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);

@@ -84,7 +84,7 @@ int list_pass(Call& c, const Source& s, const Tables& t, const AtlasPass& pass, 
     }
     {
         StageTimer st(SRCNN_STAGE_CONV12, c);
-        run_layers12(c, ws.up.data(), (int)W, (int)H, 0, (int)H, ws.c2.data(), plane, 0, (int)H);
+        run_conv12(c, ws.up.data(), (int)W, (int)H, 0, (int)H, ws.c2.data(), plane, 0, (int)H);
     }
     {
         StageTimer st(SRCNN_STAGE_CONV3, c);

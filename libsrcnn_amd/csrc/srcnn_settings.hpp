@@ -34,7 +34,7 @@
     X(B, conv12_queue,     "SRCNN_CONV12_QUEUE",     1,     "0/1", "layer 1+2: tiles drawn from a global counter vs dealt with a static stride") \
     X(B, conv12_dma,       "SRCNN_CONV12_DMA",       1,     "0/1", "layer 1+2: weights and Y tiles staged by LDS-DMA one tile ahead vs load, wait, `ds_write`") \
     X(B, conv12_prune,     "SRCNN_CONV12_PRUNE",     1,     "0/1", "layer 1+2: strict layer 2 skips the 15 near-dead layer-1 channels in every 32-pixel segment where they are all zero vs always multiplies all 64") \
-    X(B, conv12_tiers,     "SRCNN_CONV12_TIERS",     1,     "0/1", "layer 1+2: `k_conv12_tiers`, where strict layer 2 also skips the often-zero layer-1 channels {1, 3, 10, 13, 14, 16, 29} / {33, 48, 49, 52, 62} of a 32-channel block in every 32-pixel segment where they and the block's near-dead channels are all zero, vs `k_conv12_mfma`, which skips the near-dead channels only (needs `SRCNN_CONV12_DMA` and `SRCNN_CONV12_PRUNE`)") \
+    X(B, conv12_tiers,     "SRCNN_CONV12_TIERS",     1,     "0/1", "layer 1+2: the nested-tiers instance of `k_conv12_mfma`, where strict layer 2 also skips the often-zero layer-1 channels {1, 3, 10, 13, 14, 16, 29} / {33, 48, 49, 52, 62} of a 32-channel block in every 32-pixel segment where they and the block's near-dead channels are all zero, vs the instance that skips the near-dead channels only (needs `SRCNN_CONV12_DMA` and `SRCNN_CONV12_PRUNE`)") \
     X(B, conv12_spread,    "SRCNN_CONV12_SPREAD",    1,     "0/1", "layer 1+2: small launches dealt in quarter tiles over up to 4x more workgroups") \
     X(B, conv3_wdma,       "SRCNN_CONV3_WDMA",       1,     "0/1", "layer 3: packed weight image staged by LDS-DMA vs a plain loop") \
     X(B, conv3_off64,      "SRCNN_CONV3_OFF64",      0,     "0/1", "layer 3: 64-bit plane offsets (chosen automatically for planes of 4 GiB or more)") \

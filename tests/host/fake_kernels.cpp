@@ -464,8 +464,9 @@ void launch_ycc_merge(const float* Yp, const float* Cb, const float* Cr, const f
 }
 
 void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane_stride, int out_row0,
-                        int out_rows, int relax, int, hipStream_t s, unsigned long long* clk, unsigned* queue)
+                        int out_rows, int relax, bool, int, hipStream_t s, unsigned long long* clk, unsigned* queue)
 {
+    // (tiers: that instance reads and writes what the other strict ones do and computes the same bits, so one closure serves both)
     if (out_rows <= 0) return;
     if (relax) { not_modelled("a non-parity tier of layers 1+2"); return; }
     const int body = g_body.load();

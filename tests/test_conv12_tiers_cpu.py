@@ -1,7 +1,9 @@
-"""CPU checks of k_conv12_tiers' premises (the GPU side is tests/test_gpu_conv12_tiers.py): the tier masks in the kernel source
-are a nested chain that starts at M_DEAD and are the ones tools/conv12_zero_segments.py printed; the exactness argument's two
-facts about the weight table hold (no layer-2 bias is +-0, every layer-2 weight is finite); the three pinned kernel
-fingerprints did not move; the new kernel has a fingerprint of its own."""
+"""CPU checks of the premises of k_conv12_mfma's nested zero tiers (the GPU side is tests/test_gpu_conv12_tiers.py): the tier
+masks in the kernel source are a nested chain that starts at M_DEAD and are the ones tools/conv12_zero_segments.py printed; the
+exactness argument's two facts about the weight table hold (no layer-2 bias is +-0, every layer-2 weight is finite); the three
+pinned kernel fingerprints are the recorded ones, k_conv12_mfma's covers the tiers and run_conv12, and the committed traffic
+record was measured on this text."""
+import json
 import os
 import re
 
@@ -11,7 +13,7 @@ from libsrcnn_amd import build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PINNED = {
-    "k_conv12_mfma": "e6fcc3897416918d97488400ce07d743bd3884e49cc6b4b95059ed52ca0d14db",
+    "k_conv12_mfma": "94857eddbb2a8296a76ec6a18246f0288de6590de38bfd8a5f647015ee1ee39a",
     "k_conv3": "8f0b7e652c0cb756f84cfcb4c4c087ecf194afc30c362529bc70a23bf8764bd9",
     "k_rs2d_dma": "adef7f27470d21d8aa7396a314ed8a758b2707fa87b705cbb289ae66fd085030",
 }
@@ -70,8 +72,37 @@ def test_pinned_fingerprints_are_unchanged():
         assert build.kernel_source_sha(name) == sha, name
 
 
-def test_new_kernel_has_its_own_fingerprint():
-    sha = build.kernel_source_sha("k_conv12_tiers")
-    assert sha is not None and re.fullmatch(r"[0-9a-f]{64}", sha)
-    others = [build.kernel_source_sha(n) for n in ("k_conv12_mfma", "k_conv3", "k_conv3_sparse", "k_rs2d_dma")]
-    assert sha not in others
+def _sha_of_modified_copy(monkeypatch, tmp_path, file, old, new):
+    """kernel_source_sha("k_conv12_mfma") of a copy of the sources in which `old` (which occurs once) reads `new`"""
+    for f in ("srcnn_kernels.hip", "srcnn_capi.cpp"):
+        text = open(os.path.join(build.CSRC, f)).read()
+        if f == file:
+            assert text.count(old) == 1, old
+            text = text.replace(old, new)
+        (tmp_path / f).write_text(text)
+    monkeypatch.setattr(build, "CSRC", str(tmp_path))
+    return build.kernel_source_sha("k_conv12_mfma")
+
+
+def test_one_fingerprint_covers_the_tiers_and_run_conv12(monkeypatch, tmp_path):
+    """The nested-tiers instance is k_conv12_mfma's: there is no second kernel and no second fingerprint, and the one
+    fingerprint moves with the tier masks and with the host function that picks the instance."""
+    assert build.kernel_source_sha("k_conv12_tiers") is None
+    sha = build.kernel_source_sha("k_conv12_mfma")
+    _dead, tiers = kernel_tiers()
+    t2 = "0x%016xull" % tiers[-1]
+    assert _sha_of_modified_copy(monkeypatch, tmp_path, "srcnn_kernels.hip", t2, "0x%016xull" % (tiers[-1] | 1)) not in (None, sha)
+    monkeypatch.undo()
+    assert _sha_of_modified_copy(monkeypatch, tmp_path, "srcnn_capi.cpp", "const bool tiers = c.relax() == 0 &&", "const bool tiers = c.relax() != 0 &&") not in (None, sha)
+    monkeypatch.undo()
+    assert build.kernel_source_sha("k_conv12_mfma") == sha
+
+
+def test_traffic_record_carries_the_trees_fingerprints():
+    """bench.py quotes roofline.traffic and whole_path only from a record taken on this text: profiles/r06_pmc_conv12.json must
+    carry the tree's fingerprints, at top level (k_conv12_mfma) and for every kernel of `path`."""
+    rec = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_conv12.json")))
+    assert rec["kernel"] == "k_conv12_mfma" and rec["kernel_source_sha256"] == build.kernel_source_sha("k_conv12_mfma")
+    assert set(rec["path"]) == {"k_conv12_mfma", "k_conv3_sparse", "k_rs2d_dma"}
+    for name, entry in rec["path"].items():
+        assert entry["kernel_source_sha256"] == build.kernel_source_sha(name), name

@@ -1,7 +1,8 @@
-"""k_conv12_tiers, the production strict layer-1+2 kernel, chooses per 32-channel block and 32-pixel segment between the full
-layer-2 body and one body per zero tier (MT_TIER in srcnn_kernels.hip: T1 = M_DEAD, T2 = T1 + often-zero channels).  Whatever
-body a segment takes, the 32 layer-2 planes must be the oracle's conv2(conv1(.)) bit for bit; so must k_conv12_mfma's, which
-SRCNN_CONV12_TIERS=0 runs with its pruned body and SRCNN_CONV12_PRUNE=0 with the full body only.  All three go through the
+"""The nested-tiers instance of k_conv12_mfma, the production strict layer-1+2 kernel, chooses per 32-channel block and 32-pixel
+segment between the full layer-2 body and one body per zero tier (MT_TIER in srcnn_kernels.hip: T1 = M_DEAD, T2 = T1 +
+often-zero channels).  Whatever body a segment takes, the 32 layer-2 planes must be the oracle's conv2(conv1(.)) bit for bit; so
+must those of the instance without the tiers, which SRCNN_CONV12_TIERS=0 runs with the M_DEAD body and SRCNN_CONV12_PRUNE=0 with
+the full body only.  All three go through the
 stage-level layers-1+2 call (srcnn_conv12_f32_dev) on the same upscaled-Y planes.
 
 The planes are built so that every body of every block is taken, which is checked on the CPU from the oracle's layer-1
@@ -117,7 +118,7 @@ def test_inputs_take_every_body_of_every_block(reference):
 
 @pytest.mark.gpu
 def test_tiers_kernel_matches_the_oracle(srcnn, reference):
-    """The library as loaded (SRCNN_CONV12_TIERS default 1 -> k_conv12_tiers; under another setting, what that setting runs)."""
+    """The library as loaded (SRCNN_CONV12_TIERS default 1 -> the nested-tiers instance; under another setting, what that setting runs)."""
     ref, total = reference
     assert (total >= MIN_SEGMENTS).all(), total.tolist()
     for name, (p, want) in ref.items():
@@ -141,8 +142,9 @@ print('DONE')
 @pytest.mark.gpu
 @pytest.mark.parametrize("switch", ["SRCNN_CONV12_TIERS=1", "SRCNN_CONV12_TIERS=0", "SRCNN_CONV12_PRUNE=0"])
 def test_switches_match_the_oracle(reference, tmp_path, switch):
-    """Each switch in a fresh process (the switches are read when the library is loaded): k_conv12_tiers, k_conv12_mfma with
-    its pruned body (TIERS=0), and k_conv12_mfma with the full body only (PRUNE=0), all on the same planes."""
+    """Each switch in a fresh process (the switches are read when the library is loaded): the nested-tiers instance of
+    k_conv12_mfma, the instance without the tiers with its M_DEAD body (TIERS=0) and with the full body only (PRUNE=0), all on the
+    same planes."""
     ref, _total = reference
     out = str(tmp_path / "planes.npz")
     code = _CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}

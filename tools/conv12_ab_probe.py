@@ -9,7 +9,7 @@ build, and this tree's build with SRCNN_CONV12_TIERS=0.  Each child takes one 38
 repeats: min and median) and prints a checksum of the layer-2 planes and of the result, so that arms that disagree are visible
 at once.
 
-On `noise` nothing beyond M_DEAD is ever zero, so k_conv12_tiers only pays its extra compares there; bench.py's
+On `noise` nothing beyond M_DEAD is ever zero, so the nested-tiers instance of k_conv12_mfma only pays its extra compares there; bench.py's
 `generators.noise` is a 3-step figure whose run-to-run spread (1.4 %) is larger than that.  This is the instrument behind the
 `noise` lines of profiles/conv12_tiers_ab.txt (tools/conv3_ab_probe.py is its layer-3 twin).  A child that fails or runs past
 its limit ends the probe: nothing more is started on the device after it."""

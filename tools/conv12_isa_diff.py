@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 assembly of every kernel of srcnn_kernels.hip between two trees (profiles/conv12_fold_isa.txt).
+
+    python tools/conv12_isa_diff.py PARENT_TREE RESULT_TREE      (or two .s files made with the command below)
+
+Each tree's csrc/srcnn_kernels.hip is compiled device-only to assembly with the Makefile's HIPFLAGS.  A kernel's text runs from
+its label to the end of its .amdhsa_kernel block, so register counts, scratch, LDS and kernarg size are compared too.  Comments
+go, the kernel's own symbol becomes K and block labels lose their function number.  k_conv12_tiers and k_conv12_mfma<R, LD>
+are compared with the k_conv12_mfma<R, LD, TIERS> that replaced them.  Needs hipcc; no GPU."""
+import difflib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+FLAGS = ("--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -fvisibility=hidden -Wall -Wno-unused-result "
+         "-Wno-unused-value -Wno-ignored-attributes -D__HIP_PLATFORM_AMD__ --cuda-device-only -S -x hip").split()
+
+
+def assembly(path):
+    if os.path.isfile(path):
+        return open(path).read()
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "k.s")
+        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS +
+                       [os.path.join(path, "libsrcnn_amd", "csrc", "srcnn_kernels.hip"), "-o", out], check=True)
+        return open(out).read()
+
+
+def key(sym):
+    """one name for a kernel on both sides of the fold"""
+    if "k_conv12_tiers" in sym:
+        return "k_conv12_mfma<0,1,1>"
+    m = re.search(r"k_conv12_mfmaILi(\d)ELb(\d)E(?:Lb(\d)E)?EEv", sym)
+    return "k_conv12_mfma<%s,%s,%s>" % (m.group(1), m.group(2), m.group(3) or "0") if m else sym
+
+
+def kernels(asm):
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?\.amdhsa_kernel \1\n.*?\.end_amdhsa_kernel)", asm, re.M | re.S):
+        lines = [re.sub(r"\s*;.*", "", l).rstrip() for l in m.group(2).replace(m.group(1), "K").split("\n")]
+        out[key(m.group(1))] = [re.sub(r"\.L(BB|func_end|tmp)\d+", r".L\1", l) for l in lines if l.strip()]
+    return out
+
+
+def main(a, b):
+    ka, kb = kernels(assembly(a)), kernels(assembly(b))
+    print("kernels: %d / %d; only in one tree: %s" % (len(ka), len(kb), sorted(set(ka) ^ set(kb)) or "none"))
+    same = 0
+    for k in sorted(set(ka) & set(kb)):
+        d = [l for l in difflib.unified_diff(ka[k], kb[k], lineterm="", n=0) if l[0] in "+-" and l[:3] not in ("+++", "---")]
+        if d or "k_conv12" in k:
+            print("%-60s %5d / %5d lines, %d differ" % (k[:60], len(ka[k]), len(kb[k]), len(d)))
+            for l in d[:20]:
+                print("    " + l)
+        else:
+            same += 1
+    print("every other kernel (%d): 0 lines differ" % same)
+
+
+if __name__ == "__main__":
+    main(*sys.argv[1:3])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How often is a layer-1 channel all zero over one wave segment of the layer-1+2 kernel, and which channels are zero together?
 
-k_conv12_mfma / k_conv12_tiers compute one image row x 32 columns per wave step (a segment) and hand the 64 layer-1 activations
+k_conv12_mfma computes one image row x 32 columns per wave step (a segment) and hands the 64 layer-1 activations
 of those 32 pixels to layer 2 one 32-channel MFMA block at a time.  Strict layer 2 may leave out every channel it has just
 seen all +-0 over the segment.  The kernel decides once per block between a few fully unrolled bodies, so what it needs is
 a short chain of NESTED channel sets per block, T1 = M_DEAD's members of the block, T1 < T2 < T3, each as large and as

@@ -36,8 +36,6 @@ def short(name):
         tier = " [strict]"
     elif "<false" in name:
         tier = " [fast tier]"
-    if "k_conv12_tiers" in name:        # the strict path's default layer-1+2 kernel (not a template)
-        return "k_conv12_tiers [strict]"
     if "k_conv12_mfma<" in name:          # first template argument = RELAX mask: 0 strict, 3 fast tier, 1 / 2 single-layer relaxations
         r = name.split("k_conv12_mfma<")[1].split(",")[0].strip()
         return "k_conv12_mfma" + {"0": " [strict]", "3": " [fast tier]"}.get(r, " [relaxed %s]" % r)
@@ -97,19 +95,14 @@ if pmc:
     lines.append("| kernel | " + " | ".join(cols) + " |\n|---|" + "---|" * len(cols))
     for k, v in pmc.items():
         lines.append("| %s | " % k + " | ".join("%.6g" % v.get(c, float("nan")) for c in cols) + " |")
-    # layers 1+2 under the name of the kernel that RAN: k_conv12_tiers, or k_conv12_mfma with SRCNN_CONV12_TIERS=0.  The record's
-    # top-level fingerprint stays k_conv12_mfma's, which is what bench.py holds roofline.traffic to: k_conv12_tiers is that
-    # kernel's strict LDS-DMA instance with another choice of layer-2 body, its loads and stores are the same one for one
-    # (DESIGN 4.1), and its own fingerprint covers k_conv12_mfma's shared regions; `path` carries the fingerprint of what ran.
-    k12name = "k_conv12_tiers" if "k_conv12_tiers [strict]" in pmc else "k_conv12_mfma"
-    k12 = pmc.get(k12name + " [strict]")
+    k12 = pmc.get("k_conv12_mfma [strict]")
     if k12 and "FETCH_SIZE" in k12 and "WRITE_SIZE" in k12:
         n_out = 7680 * 4320
-        lpf12 = max(1, pmc_n[k12name + " [strict]"].get("FETCH_SIZE", 1))          # launches (bands) per frame
+        lpf12 = max(1, pmc_n["k_conv12_mfma [strict]"].get("FETCH_SIZE", 1))          # launches (bands) per frame
         fetch, write = k12["FETCH_SIZE"] * 1024, k12["WRITE_SIZE"] * 1024              # per launch
         sys.path.insert(0, ROOT)
         from libsrcnn_amd import build as _b
-        rec = {"kernel": k12name, "tag": tag, "kernel_source_sha256": _b.kernel_source_sha("k_conv12_mfma"), "measured_at": "tools/collect_profiles.sh %s, code at commit %s" % (tag, head),
+        rec = {"kernel": "k_conv12_mfma", "tag": tag, "kernel_source_sha256": _b.kernel_source_sha("k_conv12_mfma"), "measured_at": "tools/collect_profiles.sh %s, code at commit %s" % (tag, head),
                "fetch_bytes": fetch, "write_bytes": write,
                "launches_per_frame": lpf12,
                "hbm_bytes_per_launch": fetch + write, "algorithmic_bytes_per_launch": 132 * n_out / lpf12,
@@ -119,8 +112,8 @@ if pmc:
                        "than was requested -- so FETCH_SIZE is taken at face value.  WRITE_SIZE matches 128 B/px exactly."}
         # the other kernels of the strict path, same passes: what one 4K -> 8K frame moves through HBM in total
         # (per FRAME: per-launch average x launches per frame)
-        path = {k12name: {"fetch_bytes": fetch * lpf12, "write_bytes": write * lpf12, "launches_per_frame": lpf12,
-                          "kernel_source_sha256": _b.kernel_source_sha(k12name)}}
+        path = {"k_conv12_mfma": {"fetch_bytes": fetch * lpf12, "write_bytes": write * lpf12, "launches_per_frame": lpf12,
+                          "kernel_source_sha256": _b.kernel_source_sha("k_conv12_mfma")}}
         # layer 3 under the name and the fingerprint of the kernel that RAN (k_conv3_sparse, or k_conv3 with SRCNN_CONV3_SKIP=0):
         # bench.py holds every entry of `path` to build.kernel_source_sha(its key)
         for kname, key in (("k_conv3_sparse", "k_conv3_sparse [strict]"), ("k_conv3", "k_conv3 [strict]"),
