@@ -68,7 +68,9 @@ YUV_PACKED_RECT_SYMBOLS = ["srcnn_yuv_packed_rect_abi_version", "srcnn_yuv_packe
 RECT_LIST_SYMBOLS = ["srcnn_rect_list_abi_version", "srcnn_y_path_rect_list_plan", "srcnn_y_path_rect_list_f32_dev"]
 # a list of rectangles of an RGB(A) image (include/srcnn_amd_rgb_rect_list.h, listed in include/srcnn_amd_rgb_rect_list.abi; its own version)
 RGB_RECT_LIST_SYMBOLS = ["srcnn_rgb_rect_list_abi_version", "srcnn_rgb_upscale_rect_list_plan", "srcnn_rgb_upscale_rect_list_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
+# a list of rectangles of a planar / semi-planar YUV frame (include/srcnn_amd_yuv_rect_list.h, listed in include/srcnn_amd_yuv_rect_list.abi; its own version)
+YUV_RECT_LIST_SYMBOLS = ["srcnn_yuv_rect_list_abi_version", "srcnn_yuv_upscale_rect_list_plan", "srcnn_yuv_upscale_rect_list_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -91,6 +93,11 @@ class RgbRectItem(C.Structure):
     """srcnn_rgb_rect_item (include/srcnn_amd_rgb_rect_list.h)."""
     _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("dst", C.c_void_p * 4), ("dst_pitch", C.c_size_t * 4),
                 ("dst_conv", C.c_void_p), ("dst_conv_pitch", C.c_size_t)]
+
+
+class YuvRectItem(C.Structure):
+    """srcnn_yuv_rect_item (include/srcnn_amd_yuv_rect_list.h)."""
+    _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("dst", C.c_void_p * 3), ("dst_pitch", C.c_size_t * 3)]
 
 
 class RectListPlan(C.Structure):
@@ -202,9 +209,12 @@ def lib():
             "srcnn_rgb_rect_list_abi_version": (i, []),
             "srcnn_rgb_upscale_rect_list_plan": (i, [C.POINTER(RgbFormat), u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
             "srcnn_rgb_upscale_rect_list_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), vp, u, u, vp]),
+            "srcnn_yuv_rect_list_abi_version": (i, []),
+            "srcnn_yuv_upscale_rect_list_plan": (i, [C.POINTER(YuvFormat), u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
+            "srcnn_yuv_upscale_rect_list_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), vp, u, u, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -1137,6 +1147,90 @@ def rgb_upscale_rects(image, rects, multiply=2.0, filt=SRCNNF_Bicubic, layout=No
         out = flat[o_img:o_img + rw * rh * c * bps].view(dt).reshape((c, rh, rw) if planar else (rh, rw, c)).copy()
         res.append((out, flat[o_conv:o_conv + rw * rh * bps].view(dt).reshape(rh, rw).copy()) if want_conv else out)
     return res
+
+
+def yuv_rect_items(items):
+    """A ctypes array of srcnn_yuv_rect_item from (x0, y0, rw, rh[, dst[, dst_pitch]]) tuples, or `items` itself when it already
+    is such an array.  dst: up to 3 plane arguments (each a DeviceBuffer, a (DeviceBuffer, byte offset) pair or an address;
+    semi-planar uses the first two), dst_pitch: up to 3 byte counts or None (tight).  Returns (array or None, n)."""
+    if isinstance(items, C.Array):
+        return items, len(items)
+    items = list(items)
+    if not items:
+        return None, 0
+    arr = (YuvRectItem * len(items))()
+    for k, it in enumerate(items):
+        it = tuple(it)
+        arr[k].x0, arr[k].y0, arr[k].rw, arr[k].rh = (int(v) for v in it[:4])
+        for p, plane in enumerate(it[4] if len(it) > 4 and it[4] is not None else ()):
+            arr[k].dst[p] = _addr(plane)
+        for p, pitch in enumerate(it[5] if len(it) > 5 and it[5] is not None else ()):
+            arr[k].dst_pitch[p] = int(pitch or 0)
+    return arr, len(items)
+
+
+def yuv_upscale_rect_list_plan(fmt, w, h, multiply, filt, items, n=None, item_size=None, struct_size=None):
+    """srcnn_yuv_upscale_rect_list_plan (no device): how the YUV list call routes and packs `items` (see yuv_rect_items) at the
+    current mode, workspace limit and switches.  Returns the RectListPlan.  n / item_size / struct_size override what is passed
+    (tests)."""
+    arr, count = yuv_rect_items(items) if items is not None else (None, 0)
+    plan = RectListPlan()
+    plan.struct_size = C.sizeof(RectListPlan) if struct_size is None else int(struct_size)
+    check(lib().srcnn_yuv_upscale_rect_list_plan(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                 C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                 C.sizeof(YuvRectItem) if item_size is None else int(item_size), C.byref(plan)))
+    return plan
+
+
+def yuv_upscale_rect_list_dev(fmt, w, h, multiply, filt, src, src_pitch, items, stream=None, n=None, item_size=None):
+    """srcnn_yuv_upscale_rect_list_dev on device memory, as given: fmt, src and src_pitch as for yuv_upscale_rect_dev (the whole
+    frame), items the rects with their destinations (see yuv_rect_items).  Asynchronous on `stream` (a Stream, a raw handle or
+    None); the item array is read before the call returns.  Raises SrcnnError with the library's code."""
+    vp, sz = C.c_void_p, C.c_size_t
+    three = lambda xs, fill: list(xs) + [fill] * (3 - len(xs))   # noqa: E731
+    s = (vp * 3)(*[_addr(p) for p in three(src, None)]) if src is not None else None
+    sp = (sz * 3)(*three(src_pitch, 0)) if src_pitch is not None else None
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    arr, count = yuv_rect_items(items) if items is not None else (None, 0)
+    check(lib().srcnn_yuv_upscale_rect_list_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                s, sp, C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                C.sizeof(YuvRectItem) if item_size is None else int(item_size), handle))
+
+
+def yuv_upscale_rects(planes, rects, layout="planar", chroma="420", depth=8, msb_aligned=False, multiply=2.0, filt=SRCNNF_Bicubic):
+    """The planes of yuv_upscale_rect(planes, rect, ...) for every rect (x0, y0, rw, rh) of `rects`, through ONE
+    srcnn_yuv_upscale_rect_list_dev call: numpy planes of the whole frame in, a list of (Y', U', V') tuples out -- (Y', UV') for a
+    semi-planar format -- each shaped as yuv_upscale shapes the planes of an rw x rh frame."""
+    rects = [tuple(int(v) for v in r) for r in rects]
+    if not rects:
+        return []
+    fmt = yuv_format(layout, chroma, depth, msb_aligned)
+    dt = np.uint8 if depth == 8 else np.uint16
+    y = np.ascontiguousarray(planes[0], dt)
+    h, w = y.shape
+    n = 2 if fmt.layout == YUV_SEMIPLANAR else 3
+    src_sizes = [yuv_plane_size(fmt, w, h, k) for k in range(n)]
+    bps = np.dtype(dt).itemsize
+    ins = [y] + [np.ascontiguousarray(p, dt).reshape(r, rb // bps) for p, (_c, r, rb) in zip(planes[1:], src_sizes[1:])]
+    assert len(ins) == n, "%d planes given, the format has %d" % (len(ins), n)
+    din = [DeviceBuffer.from_numpy(p) for p in ins]
+    layouts, total = [], 0                       # per item and plane: (byte offset, shape), each plane from a 16-byte boundary
+    for (_, _, rw, rh) in rects:
+        one = []
+        for k in range(n):
+            if rw <= 0 or rh <= 0:
+                one.append((total, (0, 0)))      # (for the library to refuse)
+                continue
+            _c, r, rb = yuv_plane_size(fmt, rw, rh, k)
+            one.append((total, (r, rb // bps)))
+            total += (r * rb + 15) & ~15
+        layouts.append(one)
+    dout = DeviceBuffer(max(16, total))
+    items = [(x0, y0, rw, rh, [(dout, o) for o, _ in one], None) for (x0, y0, rw, rh), one in zip(rects, layouts)]
+    yuv_upscale_rect_list_dev(fmt, w, h, multiply, filt, din, None, items)
+    sync()
+    flat = dout.to_numpy(np.uint8, (max(16, total),))
+    return [tuple(flat[o:o + sh[0] * sh[1] * bps].view(dt).reshape(sh).copy() for o, sh in one) for one in layouts]
 
 
 def _one_hip_runtime():

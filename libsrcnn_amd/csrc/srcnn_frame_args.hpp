@@ -290,6 +290,41 @@ inline int check_yuv_rect_origin(const YuvGeom& g, unsigned x0, unsigned y0)
 // srcnn_yuv_upscale_rect_dev: the rules of check_yuv_args with the WHOLE w x h frame as the source and the planes of an rw x rh
 // frame as the destination, the rect's own rules between the scale and the planes, and -- unlike the whole-frame calls --
 // destination planes that overlap each other refused (a rect is repainted inside a shared surface: a slip shows here first).
+// It comes in a frame half and a per-rect half, which the YUV rect LIST call (srcnn_yuv_rect_list_call.cpp) runs once and once
+// per item: describe_yuv_side for the source, then check_yuv_rect_place and check_yuv_rect_planes for every rect.
+
+// One side ("input" / "output") of a planar / semi-planar call: the planes of a pw x ph frame in g
+inline int describe_yuv_side(const YuvGeom& g, unsigned pw, unsigned ph, const void* const base[3], const size_t pitch[3], const char* side,
+                             YuvPlane p[3])
+{
+    const unsigned pcw = g.ccols(pw), pch = g.crows(ph);
+    int rc;
+    for (int k = 0; k < (g.semi ? 2 : 3); ++k) {
+        const size_t row_bytes = (size_t)g.bps * (k == 0 ? pw : (g.semi ? 2 * (size_t)pcw : pcw));
+        if ((rc = describe_plane(p[k], base[k], pitch ? pitch[k] : 0, row_bytes, k == 0 ? ph : pch, g.bps, side, k))) return rc;
+    }
+    return SRCNN_OK;
+}
+
+// per rect, geometry: not empty, inside dw x dh, an origin the chroma grid can express
+inline int check_yuv_rect_place(const YuvGeom& g, unsigned dw, unsigned dh, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
+{
+    int rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    return check_yuv_rect_origin(g, x0, y0);
+}
+
+// per rect, memory: the planes of an rw x rh frame as the destination, against the source planes `in` and each other
+inline int check_yuv_rect_planes(const YuvGeom& g, unsigned rw, unsigned rh, void* const dst[3], const size_t dst_pitch[3], const YuvPlane in[3],
+                                 YuvPlane out[3])
+{
+    const int np = g.semi ? 2 : 3;
+    int rc;
+    if ((rc = describe_yuv_side(g, rw, rh, dst, dst_pitch, "output", out))) return rc;
+    if ((rc = check_in_out_overlap(in, np, out, np))) return rc;
+    return check_out_out_overlap(out, np);
+}
+
 inline int check_yuv_rect_args(const YuvGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* const src[3],
                                const size_t src_pitch[3], unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* const dst[3],
                                const size_t dst_pitch[3], unsigned& dw, unsigned& dh, YuvPlane in[3], YuvPlane out[3])
@@ -301,19 +336,9 @@ inline int check_yuv_rect_args(const YuvGeom& g, unsigned w, unsigned h, float m
     if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
     int rc;
     if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
-    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
-    if ((rc = check_yuv_rect_origin(g, x0, y0))) return rc;
-    for (int side = 0; side < 2; ++side) {
-        const unsigned pw = side ? rw : w, ph = side ? rh : h, pcw = g.ccols(pw), pch = g.crows(ph);
-        const size_t* pitch = side ? dst_pitch : src_pitch;
-        for (int k = 0; k < np; ++k) {
-            const size_t row_bytes = (size_t)g.bps * (k == 0 ? pw : (g.semi ? 2 * (size_t)pcw : pcw));
-            if ((rc = describe_plane((side ? out : in)[k], side ? dst[k] : src[k], pitch ? pitch[k] : 0, row_bytes, k == 0 ? ph : pch,
-                                     g.bps, side ? "output" : "input", k))) return rc;
-        }
-    }
-    if ((rc = check_in_out_overlap(in, np, out, np))) return rc;
-    return check_out_out_overlap(out, np);
+    if ((rc = check_yuv_rect_place(g, dw, dh, x0, y0, rw, rh))) return rc;
+    if ((rc = describe_yuv_side(g, w, h, src, src_pitch, "input", in))) return rc;
+    return check_yuv_rect_planes(g, rw, rh, dst, dst_pitch, in, out);
 }
 
 // The unit rule of a packed span (include/srcnn_amd_yuv_packed_rect.h): pixels [x, x + n) of a `width`-pixel row, already known

@@ -341,6 +341,9 @@ namespace {
 //            k_yuv_window_chroma from the integer source.  Everything else, and SRCNN_YUV_RECT_UNFUSED=1: the plane route over the
 //            window: unpack of the chroma source rectangle -> resample_window per plane -> pack.
 // Both read no sample outside the rectangles srcnn_yuv_rect_source reports, and both give the bytes of yuv_frame.
+// (Declared in srcnn_host.hpp: the single items of the YUV rect list call, srcnn_yuv_rect_list_call.cpp, run it too.)
+}  // namespace
+
 int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
              const YuvPlane out[3], unsigned x0, unsigned y0, unsigned x1, unsigned y1)
 {
@@ -401,6 +404,8 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
         return SRCNN_OK;
     });
 }
+
+namespace {
 
 // Luma columns [x0, x1) (under the unit rule) of rows [y0, y1) of what yuv_packed_frame writes, at the cost of the rect.  out is
 // the rect's own row segments: out.row_bytes bytes (yuv_packed_span of the rect) per row, the byte of pixel (x0, y0) first.  A

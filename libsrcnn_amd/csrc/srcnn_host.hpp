@@ -371,6 +371,11 @@ struct RgbRule;
 struct YuvPlane;
 int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[4],
              const YuvPlane out[4], const YuvPlane& conv, unsigned x0, unsigned y0, unsigned x1, unsigned y1);
+// The YUV rect call behind srcnn_yuv_upscale_rect_dev (srcnn_frames.cpp), arguments checked: the luma rect [x0,x1) x [y0,y1) and
+// the chroma samples that cover it into out[], the rect's own planes.
+struct YuvGeom;
+int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
+             const YuvPlane out[3], unsigned x0, unsigned y0, unsigned x1, unsigned y1);
 // (axis_source_span, the source span of a range of an axis without a device, is srcnn_rect_source.hpp)
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);

@@ -169,7 +169,7 @@ inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteI
     return route;
 }
 
-// The same with one more condition on a batched item: extra(rect) (the colour shell of srcnn_rgb_rect_atlas.hpp)
+// The same with one more condition on a batched item: extra(rect) (the colour shells of srcnn_rgb_rect_atlas.hpp and srcnn_yuv_rect_atlas.hpp)
 template <class Extra>
 inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteInputs& in, Extra extra)
 {

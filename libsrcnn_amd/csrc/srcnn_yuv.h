@@ -34,6 +34,24 @@ void launch_yuv_window_chroma(const unsigned char* const src[2], const size_t sp
                               const Yuv16Rule* f, unsigned cx0, unsigned cy0, unsigned cols, unsigned rows, const DevAxisTable& th,
                               const DevAxisTable& tv, unsigned char* const dst[2], const size_t dpitch[2], hipStream_t s);
 
+// ---- the three kernels of the rect LIST call (srcnn_yuv_rect_list.hip; include/srcnn_amd_yuv_rect_list.h) ----
+struct ListCellDesc;         // srcnn_rect_atlas.hpp
+struct YuvListDstDesc;       // srcnn_yuv_rect_atlas.hpp
+// launch_list_resample (srcnn_rect_list.h) reading Y off the pitched integer luma plane src (the WHOLE w x h plane) as
+// launch_plane_unpack reads luma.  th, tv: the Y tables.  f as for launch_plane_unpack.
+void launch_yuv_list_resample(const unsigned char* src, size_t spitch, unsigned w, unsigned h, const Yuv16Rule* f, const DevAxisTable& th,
+                              const DevAxisTable& tv, const ListCellDesc* d, unsigned ncells, const ListCellDesc& end, float* atlas,
+                              unsigned atlas_w, hipStream_t s);
+// Every rect of a pass: Y' of the atlas result written as launch_plane_pack writes luma (sat = false) where dd (the device copy
+// of the pass's destination table, entry k for cell k) points.
+void launch_yuv_list_luma(const Yuv16Rule* f, const ListCellDesc* d, const YuvListDstDesc* dd, unsigned ncells, const ListCellDesc& end,
+                          const float* atlas, unsigned atlas_w, hipStream_t s);
+// Every chroma rect of a pass: launch_yuv_window_chroma for the chroma rect and the planes of each entry of dd; `end`: the
+// table's closing entry (the tile total).  The router has asked window_tile_fits for every chroma rect.
+void launch_yuv_list_chroma(const unsigned char* const src[2], const size_t spitch[2], unsigned cw, unsigned ch, bool semi, const Yuv16Rule* f,
+                            const DevAxisTable& cth, const DevAxisTable& ctv, const YuvListDstDesc* dd, unsigned ncells,
+                            const YuvListDstDesc& end, hipStream_t s);
+
 // ---- packed frames: one plane that interleaves Y, U, V (and A) (srcnn_yuv_packed.hip) ----
 // Packed rows [0, rows) of `w` pixels -> tight float planes: dy (w per row, scaled by f.down), du / dv (ceil(w/2) per row for
 // the 4:2:2 kinds, else w; native scale), da (w per row; only where f.amask).  Base and pitch must have the format's alignment.

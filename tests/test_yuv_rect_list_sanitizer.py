@@ -1,0 +1,35 @@
+"""CPU: the host half of the planar / semi-planar YUV rect list call under AddressSanitizer + UBSan.
+
+tests/host/yuv_rect_list_sanitize.cpp is a stand-alone program (its own main, no GPU, no HIP) that drives the router with the
+chroma condition and the destination table of csrc/srcnn_yuv_rect_atlas.hpp -- the code srcnn_yuv_upscale_rect_list_plan and
+srcnn_yuv_upscale_rect_list_dev both run -- over seeded lists in every cell (4:2:0 / 4:2:2 / 4:4:4, planar and semi-planar, 1 / 2
+bytes per sample).  It asserts that every destination entry belongs to exactly one batched item, that its chroma rect is
+YuvChromaRect of the item, that the chroma tile prefix counts each item's tiles once and ends at the closing entry's total, that
+the bytes an entry lets the two store kernels write -- recomputed from the descriptors alone -- are the item's rows at its
+pitches, that a vector flag is set only where base and pitch are multiples of the store size, that an item whose chroma window
+does not fit is routed single, and that a frame whose chroma axis keeps its size routes every item single.  It is built here
+exactly as tests/test_rgb_rect_list_sanitizer.py builds its program and run as a process of its own; nothing of it is loaded into
+Python."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_yuv_rect_list_host_code_under_asan_and_ubsan(tmp_path):
+    if not shutil.which("g++"):
+        pytest.skip("no host toolchain")
+    exe = str(tmp_path / "yuv_rect_list_asan")
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "host", "yuv_rect_list_sanitize.cpp"), "-lm", "-o", exe],
+                       capture_output=True, text=True, timeout=600)
+    if r.returncode != 0 and ("cannot find -lasan" in r.stderr or "libasan" in r.stderr and "No such file" in r.stderr):
+        pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
+    assert r.returncode == 0, r.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:alloc_dealloc_mismatch=1:strict_string_checks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "all checks passed" in r.stdout
