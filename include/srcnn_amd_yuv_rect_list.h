@@ -7,7 +7,7 @@
  * An EXTENSION of the stable ABI (include/srcnn_amd.h) beside include/srcnn_amd_yuv_rect.h, include/srcnn_amd_rect_list.h and
  * include/srcnn_amd_rgb_rect_list.h, with a version of its own: the functions declared here are listed in
  * include/srcnn_amd_yuv_rect_list.abi, and tests/test_yuv_rect_list_abi.py holds header, list, binding and the library's export
- * table to each other.  The older headers are unchanged.  Packed formats (include/srcnn_amd_yuv_packed_rect.h) have no list form.
+ * table to each other.  The older headers are unchanged.  Packed formats (include/srcnn_amd_yuv_packed_rect.h) are not served here.
  *
  * Result.  After the call item k holds exactly what
  *     srcnn_yuv_upscale_rect_dev(fmt, w, h, multiply, filter, src, src_pitch, x0, y0, rw, rh, dst, dst_pitch, stream)

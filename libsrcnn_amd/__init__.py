@@ -70,7 +70,10 @@ RECT_LIST_SYMBOLS = ["srcnn_rect_list_abi_version", "srcnn_y_path_rect_list_plan
 RGB_RECT_LIST_SYMBOLS = ["srcnn_rgb_rect_list_abi_version", "srcnn_rgb_upscale_rect_list_plan", "srcnn_rgb_upscale_rect_list_dev"]
 # a list of rectangles of a planar / semi-planar YUV frame (include/srcnn_amd_yuv_rect_list.h, listed in include/srcnn_amd_yuv_rect_list.abi; its own version)
 YUV_RECT_LIST_SYMBOLS = ["srcnn_yuv_rect_list_abi_version", "srcnn_yuv_upscale_rect_list_plan", "srcnn_yuv_upscale_rect_list_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
+# a list of rectangles of a packed YUV frame (include/srcnn_amd_yuv_packed_rect_list.h, listed in include/srcnn_amd_yuv_packed_rect_list.abi; its own version)
+YUV_PACKED_RECT_LIST_SYMBOLS = ["srcnn_yuv_packed_rect_list_abi_version", "srcnn_yuv_packed_upscale_rect_list_plan",
+                                "srcnn_yuv_packed_upscale_rect_list_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -98,6 +101,11 @@ class RgbRectItem(C.Structure):
 class YuvRectItem(C.Structure):
     """srcnn_yuv_rect_item (include/srcnn_amd_yuv_rect_list.h)."""
     _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("dst", C.c_void_p * 3), ("dst_pitch", C.c_size_t * 3)]
+
+
+class YuvPackedRectItem(C.Structure):
+    """srcnn_yuv_packed_rect_item (include/srcnn_amd_yuv_packed_rect_list.h)."""
+    _fields_ = [("x0", C.c_uint), ("y0", C.c_uint), ("rw", C.c_uint), ("rh", C.c_uint), ("dst", C.c_void_p), ("dst_pitch", C.c_size_t)]
 
 
 class RectListPlan(C.Structure):
@@ -212,9 +220,12 @@ def lib():
             "srcnn_yuv_rect_list_abi_version": (i, []),
             "srcnn_yuv_upscale_rect_list_plan": (i, [C.POINTER(YuvFormat), u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
             "srcnn_yuv_upscale_rect_list_dev": (i, [C.POINTER(YuvFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), vp, u, u, vp]),
+            "srcnn_yuv_packed_rect_list_abi_version": (i, []),
+            "srcnn_yuv_packed_upscale_rect_list_plan": (i, [i, u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
+            "srcnn_yuv_packed_upscale_rect_list_dev": (i, [i, u, u, f, i, vp, sz, vp, u, u, vp]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -1231,6 +1242,83 @@ def yuv_upscale_rects(planes, rects, layout="planar", chroma="420", depth=8, msb
     sync()
     flat = dout.to_numpy(np.uint8, (max(16, total),))
     return [tuple(flat[o:o + sh[0] * sh[1] * bps].view(dt).reshape(sh).copy() for o, sh in one) for one in layouts]
+
+
+def yuv_packed_rect_items(items):
+    """A ctypes array of srcnn_yuv_packed_rect_item from (x0, y0, rw, rh[, dst[, dst_pitch]]) tuples, or `items` itself when it
+    already is such an array.  dst: a DeviceBuffer, a (DeviceBuffer, byte offset) pair or an address; dst_pitch: bytes or None
+    (tight).  Returns (array or None, n)."""
+    if isinstance(items, C.Array):
+        return items, len(items)
+    items = list(items)
+    if not items:
+        return None, 0
+    arr = (YuvPackedRectItem * len(items))()
+    for k, it in enumerate(items):
+        it = tuple(it)
+        arr[k].x0, arr[k].y0, arr[k].rw, arr[k].rh = (int(v) for v in it[:4])
+        if len(it) > 4 and it[4] is not None:
+            arr[k].dst = _addr(it[4])
+        arr[k].dst_pitch = int(it[5] or 0) if len(it) > 5 else 0
+    return arr, len(items)
+
+
+def yuv_packed_upscale_rect_list_plan(fmt, w, h, multiply, filt, items, n=None, item_size=None, struct_size=None):
+    """srcnn_yuv_packed_upscale_rect_list_plan (no device): how the packed YUV list call routes and packs `items` (see
+    yuv_packed_rect_items) at the current mode, workspace limit and switches.  Returns the RectListPlan.  n / item_size /
+    struct_size override what is passed (tests)."""
+    arr, count = yuv_packed_rect_items(items) if items is not None else (None, 0)
+    plan = RectListPlan()
+    plan.struct_size = C.sizeof(RectListPlan) if struct_size is None else int(struct_size)
+    check(lib().srcnn_yuv_packed_upscale_rect_list_plan(_yuvp_format(fmt), int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                        C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                        C.sizeof(YuvPackedRectItem) if item_size is None else int(item_size), C.byref(plan)))
+    return plan
+
+
+def yuv_packed_upscale_rect_list_dev(fmt, w, h, multiply, filt, src, src_pitch, items, stream=None, n=None, item_size=None):
+    """srcnn_yuv_packed_upscale_rect_list_dev on device memory, as given: fmt, src and src_pitch as for
+    yuv_packed_upscale_rect_dev (the whole frame), items the rects with their destinations (see yuv_packed_rect_items).
+    Asynchronous on `stream` (a Stream, a raw handle or None); the item array is read before the call returns.  Raises SrcnnError
+    with the library's code."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    arr, count = yuv_packed_rect_items(items) if items is not None else (None, 0)
+    check(lib().srcnn_yuv_packed_upscale_rect_list_dev(_yuvp_format(fmt), int(w), int(h), float(np.float32(multiply)), int(filt),
+                                                       _addr(src) if src is not None else None, int(src_pitch or 0),
+                                                       C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
+                                                       C.sizeof(YuvPackedRectItem) if item_size is None else int(item_size), handle))
+
+
+def yuv_packed_upscale_rects(src, name, w, rects, multiply=2.0, filt=SRCNNF_Bicubic):
+    """The row segments of yuv_packed_upscale_rect(src, name, w, rect, ...) for every rect (x0, y0, rw, rh) of `rects`, through
+    ONE srcnn_yuv_packed_upscale_rect_list_dev call: the whole packed frame in (a (h, row bytes) uint8 array of format `name`), a
+    list of (rh, bytes) uint8 arrays out, bytes as yuv_packed_span_bytes(name, dw, x0, rw) gives them."""
+    rects = [tuple(int(v) for v in r) for r in rects]
+    if not rects:
+        return []
+    frame = np.ascontiguousarray(src, np.uint8)
+    rb, _ = yuv_packed_row_bytes(name, w)
+    if frame.ndim != 2 or frame.shape[1] != rb:
+        raise ValueError("a %d-pixel row of this format has %d bytes: the frame is %r" % (w, rb, frame.shape))
+    h = frame.shape[0]
+    dw, _dh = output_size(w, h, multiply)
+    din = DeviceBuffer.from_numpy(frame)
+    layouts, total = [], 0                       # per item: (byte offset, (rows, bytes)), each from a 16-byte boundary
+    for (x0, y0, rw, rh) in rects:
+        nb = 0
+        if rw > 0 and rh > 0:
+            try:
+                _unit, _off, nb = yuv_packed_span_bytes(name, dw, x0, rw)
+            except SrcnnError:
+                nb = 0                           # (for the call below to refuse, with its own message)
+        layouts.append((total, (max(rh, 0) if nb else 0, nb)))
+        total += (max(rh, 0) * nb + 15) & ~15
+    dout = DeviceBuffer(max(16, total))
+    items = [(x0, y0, rw, rh, (dout, o), 0) for (x0, y0, rw, rh), (o, _sh) in zip(rects, layouts)]
+    yuv_packed_upscale_rect_list_dev(name, w, h, multiply, filt, din, 0, items)
+    sync()
+    flat = dout.to_numpy(np.uint8, (max(16, total),))
+    return [flat[o:o + sh[0] * sh[1]].reshape(sh).copy() for o, sh in layouts]
 
 
 def _one_hip_runtime():

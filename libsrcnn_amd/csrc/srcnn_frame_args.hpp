@@ -354,7 +354,35 @@ inline int check_yuv_packed_unit(const YuvPackedGeom& g, unsigned width, unsigne
 }
 
 // srcnn_yuv_packed_upscale_rect_dev: the rules of check_yuv_packed_args with the WHOLE w x h frame as the source and rh row
-// segments of the rect's span as the destination, the rect's own rules between the scale and the planes.
+// segments of the rect's span as the destination, the rect's own rules between the scale and the planes.  It comes in a frame
+// half and a per-rect half, which the packed rect LIST call (srcnn_yuv_packed_rect_list_call.cpp) runs once and once per item:
+// describe_yuv_packed_source for the frame, then check_yuv_packed_rect_place and check_yuv_packed_rect_dst for every rect.
+
+// the frame: the WHOLE w x h packed source
+inline int describe_yuv_packed_source(const YuvPackedGeom& g, unsigned w, unsigned h, const void* src, size_t src_pitch, YuvPlane& in)
+{
+    return describe_plane(in, src, src_pitch, g.row_bytes(w), h, g.align, "input", 0);
+}
+
+// per rect, geometry: not empty, inside dw x dh, under the unit rule
+inline int check_yuv_packed_rect_place(const YuvPackedGeom& g, unsigned dw, unsigned dh, unsigned x0, unsigned y0, unsigned rw, unsigned rh)
+{
+    int rc;
+    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
+    return check_yuv_packed_unit(g, dw, x0, rw);
+}
+
+// per rect, memory: rh row segments of the rect's span as the destination, against the source `in`
+inline int check_yuv_packed_rect_dst(const YuvPackedGeom& g, unsigned dw, unsigned x0, unsigned rw, unsigned rh, void* dst, size_t dst_pitch,
+                                     const YuvPlane& in, YuvPlane& out)
+{
+    int rc;
+    size_t off = 0, n = 0;
+    yuv_packed_span(g.rule.kind, dw, x0, rw, off, n);
+    if ((rc = describe_plane(out, dst, dst_pitch, n, rh, g.align, "output", 0))) return rc;
+    return check_in_out_overlap(&in, 1, &out, 1);
+}
+
 inline int check_yuv_packed_rect_args(const YuvPackedGeom& g, unsigned w, unsigned h, float multiply, int filter, const void* src,
                                       size_t src_pitch, unsigned x0, unsigned y0, unsigned rw, unsigned rh, void* dst, size_t dst_pitch,
                                       unsigned& dw, unsigned& dh, YuvPlane& in, YuvPlane& out)
@@ -363,13 +391,9 @@ inline int check_yuv_packed_rect_args(const YuvPackedGeom& g, unsigned w, unsign
     if (rw == 0 || rh == 0) return fail(SRCNN_E_ARG, "empty rect %ux%u", rw, rh);
     int rc;
     if ((rc = check_scale(w, h, multiply, filter, dw, dh))) return rc;
-    if ((rc = check_rect_inside(dw, dh, x0, y0, rw, rh))) return rc;
-    if ((rc = check_yuv_packed_unit(g, dw, x0, rw))) return rc;
-    size_t off = 0, n = 0;
-    yuv_packed_span(g.rule.kind, dw, x0, rw, off, n);
-    if ((rc = describe_plane(in, src, src_pitch, g.row_bytes(w), h, g.align, "input", 0))) return rc;
-    if ((rc = describe_plane(out, dst, dst_pitch, n, rh, g.align, "output", 0))) return rc;
-    return check_in_out_overlap(&in, 1, &out, 1);
+    if ((rc = check_yuv_packed_rect_place(g, dw, dh, x0, y0, rw, rh))) return rc;
+    if ((rc = describe_yuv_packed_source(g, w, h, src, src_pitch, in))) return rc;
+    return check_yuv_packed_rect_dst(g, dw, x0, rw, rh, dst, dst_pitch, in, out);
 }
 
 }  // namespace srcnn

@@ -2,6 +2,7 @@
 // (srcnn_frame_args.hpp) and the launchers take (srcnn_yuv.h, srcnn_rgb.h).  No HIP: the host-only sanitizer harness includes it.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 namespace srcnn {
 
@@ -75,6 +76,25 @@ inline void yuv_packed_span(int kind, unsigned width, unsigned x, unsigned n, si
 }
 // the chroma tile width of k_yuvp_window_merge: 64, or 60 (20 groups of 3) for v210
 inline unsigned yuv_packed_tile_cols(int kind) { return kind == kPkV210 ? 60u : 64u; }
+// bytes [blo, bhi) of a row of the w-pixel frame that hold luma columns [lx, hx) widened outward to the unit and cut at w
+inline void yuv_packed_unit_span(int kind, unsigned w, unsigned lx, unsigned hx, unsigned& blo, unsigned& bhi)
+{
+    const unsigned unit = yuv_packed_unit(kind);
+    lx -= lx % unit;
+    hx = (hx + unit - 1) / unit * unit;
+    if (hx > w) hx = w;
+    size_t off = 0, n = 0;
+    yuv_packed_span(kind, w, lx, hx - lx, off, n);
+    blo = (unsigned)off;
+    bhi = (unsigned)(off + n);
+}
+// how the packed side of a launch is addressed: 16-byte vectors, or pieces of 4, 2 or 1 bytes -- by what base and pitch share
+enum { kIoVec = 0, kIoDword = 4, kIoWord = 2, kIoByte = 1 };
+inline int io_of(const void* base, size_t pitch)
+{
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(base) | (uintptr_t)pitch;
+    return bits % 16 == 0 ? kIoVec : bits % 4 == 0 ? kIoDword : bits % 2 == 0 ? kIoWord : kIoByte;
+}
 
 // ---- RGB(A) images (include/srcnn_amd_rgb.h): what a srcnn_rgb_format comes down to (s = depth - 8) ----
 struct RgbRule {

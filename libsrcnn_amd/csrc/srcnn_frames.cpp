@@ -405,8 +405,6 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
     });
 }
 
-namespace {
-
 // Luma columns [x0, x1) (under the unit rule) of rows [y0, y1) of what yuv_packed_frame writes, at the cost of the rect.  out is
 // the rect's own row segments: out.row_bytes bytes (yuv_packed_span of the rect) per row, the byte of pixel (x0, y0) first.  A
 // packed row mixes luma and chroma, so chroma and alpha are merged per band of Y', not once per rect.
@@ -415,6 +413,7 @@ namespace {
 //   everything else, and SRCNN_YUV_PACKED_RECT_UNFUSED=1:  the plane route over the window: unpack of the unit-aligned source
 //       rectangle -> per band { y_path_rect, resample_window per chroma / alpha plane, pack into the row segments }
 // Both read no byte outside the rectangle srcnn_yuv_packed_rect_source reports, and both give the bytes of yuv_packed_frame.
+// (Declared in srcnn_host.hpp: the single items of the packed rect list call, srcnn_yuv_packed_rect_list_call.cpp, run it too.)
 int yuv_packed_rect(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane& in,
                     const YuvPlane& out, unsigned x0, unsigned y0, unsigned x1, unsigned y1)
 {
@@ -478,7 +477,6 @@ int yuv_packed_rect(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, uns
     });
 }
 
-}  // namespace
 }  // namespace srcnn
 
 using namespace srcnn;

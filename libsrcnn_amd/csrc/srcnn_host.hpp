@@ -376,6 +376,11 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
 struct YuvGeom;
 int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane in[3],
              const YuvPlane out[3], unsigned x0, unsigned y0, unsigned x1, unsigned y1);
+// The packed YUV rect call behind srcnn_yuv_packed_upscale_rect_dev (srcnn_frames.cpp), arguments checked: luma columns [x0,x1)
+// (under the unit rule) of rows [y0,y1) into out, the rect's own row segments of out.row_bytes bytes.
+struct YuvPackedGeom;
+int yuv_packed_rect(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const YuvPlane& in,
+                    const YuvPlane& out, unsigned x0, unsigned y0, unsigned x1, unsigned y1);
 // (axis_source_span, the source span of a range of an axis without a device, is srcnn_rect_source.hpp)
 // source rows [lo, hi) of a (w x h) plane that output rows [r0, r1) of the Y path (resample + 3 layers) depend on
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi);

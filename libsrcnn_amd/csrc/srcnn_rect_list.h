@@ -1,5 +1,6 @@
 // srcnn_rect_list.h -- launchers of the rect list call's kernels (srcnn_rect_list.hip), for srcnn_capi.cpp, and the device code
-// those kernels share with the RGB(A) list's (srcnn_rgb_rect_list.hip) and the YUV list's (srcnn_yuv_rect_list.hip).  Internal.
+// those kernels share with the RGB(A) list's (srcnn_rgb_rect_list.hip), the YUV list's (srcnn_yuv_rect_list.hip) and the packed
+// YUV list's (srcnn_yuv_packed_rect_list.hip).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +34,7 @@ __device__ __forceinline__ unsigned find_cell(const ListCellDesc* __restrict__ d
     return lo;
 }
 
-// The body of the resample kernels of all three lists: workgroup blockIdx.x takes one 64 x 16 tile of the in-plane part of one cell
+// The body of the resample kernels of all four lists: workgroup blockIdx.x takes one 64 x 16 tile of the in-plane part of one cell
 // and writes its samples of the upscaled plane into the atlas.  fetch(source row, source column, float v[1]) gives a source
 // sample of the w x h plane as a float: the one part that belongs to the caller's format.  Every return ahead of a barrier
 // depends on the cell and the tile alone, which are the same for all threads of the workgroup.

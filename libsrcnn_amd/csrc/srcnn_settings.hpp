@@ -49,7 +49,8 @@
     X(B, rect_list_unfused, "SRCNN_RECT_LIST_UNFUSED", 0,   "0/1", "rect list call: every item as a single rect call instead of the windows of small rects packed into one atlas per layer launch") \
     X(I, rect_list_single_samples, "SRCNN_RECT_LIST_SINGLE_SAMPLES", 2097152, "samples of a cell, (rw + 12) x (rh + 12)", "rect list call: items whose cell has at least this many samples run as single rect calls.  Started at 524288 (512 tiles of 64x16, one round of the persistent layer-1+2 grid); the sweep of `profiles/rect_list_probe.txt` found no crossover there -- 16 rects of 768x768 and 1024x1024 were still 1.4x and 1.3x faster batched than looped -- so it stands at 2^21, the largest cell that sweep measures.  The RGB(A) and the YUV rect list calls route by the same threshold") \
     X(B, rgb_rect_list_unfused, "SRCNN_RGB_RECT_LIST_UNFUSED", 0, "0/1", "RGB(A) rect list call: every item as a single RGB(A) rect call instead of small rects sharing one atlas per layer launch, with Y read and colour merged by `k_rgb_list_resample` / `k_rgb_list_merge`") \
-    X(B, yuv_rect_list_unfused, "SRCNN_YUV_RECT_LIST_UNFUSED", 0, "0/1", "planar / semi-planar YUV rect list call: every item as a single YUV rect call instead of small rects sharing one atlas per layer launch, with luma read and written by `k_yuv_list_resample` / `k_yuv_list_luma` and chroma by `k_yuv_list_chroma`")
+    X(B, yuv_rect_list_unfused, "SRCNN_YUV_RECT_LIST_UNFUSED", 0, "0/1", "planar / semi-planar YUV rect list call: every item as a single YUV rect call instead of small rects sharing one atlas per layer launch, with luma read and written by `k_yuv_list_resample` / `k_yuv_list_luma` and chroma by `k_yuv_list_chroma`") \
+    X(B, yuv_packed_rect_list_unfused, "SRCNN_YUV_PACKED_RECT_LIST_UNFUSED", 0, "0/1", "packed YUV rect list call: every item as a single packed YUV rect call instead of small rects sharing one atlas per layer launch, with luma read by `k_yuvp_list_resample` and chroma / alpha resampled, merged with Y' and stored by `k_yuvp_list_merge`")
 
 namespace srcnn {
 

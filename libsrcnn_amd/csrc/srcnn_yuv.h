@@ -79,4 +79,18 @@ void launch_yuvp_window_merge(const YuvPackedRule& f, const unsigned char* src, 
                               unsigned cx0, unsigned gy0, unsigned rw, unsigned ccols, unsigned rows, const DevAxisTable& th,
                               const DevAxisTable& tv, unsigned char* dst, size_t dpitch, unsigned row0, size_t span_bytes, hipStream_t s);
 
+// ---- the two kernels of the packed rect LIST call (srcnn_yuv_packed_rect_list.hip; include/srcnn_amd_yuv_packed_rect_list.h) ----
+struct YuvPackedListDstDesc; // srcnn_yuv_packed_rect_atlas.hpp
+// launch_list_resample (srcnn_rect_list.h) reading Y off the WHOLE packed w x h frame src as launch_yuvp_window_y reads it, one
+// dword per sample.  th, tv: the Y tables.
+void launch_yuvp_list_resample(const YuvPackedRule& f, const unsigned char* src, size_t spitch, unsigned w, unsigned h, const DevAxisTable& th,
+                               const DevAxisTable& tv, const ListCellDesc* d, unsigned ncells, const ListCellDesc& end, float* atlas,
+                               unsigned atlas_w, hipStream_t s);
+// Every rect of a pass: launch_yuvp_window_merge for all rows of the rect of each entry of dd (the device copy of the pass's
+// destination table, entry k for cell k of d), Y' read from the cell of the layer-3 atlas; `end`: the table's closing entry (the
+// tile total).  cth, ctv: the chroma tables (dcw <- cw), (dh <- h).  The router has asked yuvp_window_fits for every item.
+void launch_yuvp_list_merge(const YuvPackedRule& f, const unsigned char* src, size_t spitch, unsigned w, unsigned h, const DevAxisTable& cth,
+                            const DevAxisTable& ctv, const ListCellDesc* d, const YuvPackedListDstDesc* dd, unsigned ncells,
+                            const YuvPackedListDstDesc& end, const float* atlas, unsigned atlas_w, hipStream_t s);
+
 }  // namespace srcnn

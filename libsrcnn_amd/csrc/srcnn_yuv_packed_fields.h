@@ -1,8 +1,9 @@
 // srcnn_yuv_packed_fields.h -- the six memory layouts of the packed YUV formats (YuvPackedKind), each stated ONCE: the samples of
-// a 16-byte chunk (PkShape), its four dwords <-> field values (decode, encode), the dword access in pieces of the alignment a
-// frame has (load_dword, store_dword, io_of) and the float -> field conversion of the pack side (to_word).  The whole-frame
-// kernels (srcnn_yuv_packed.hip: k_yuvp_unpack, k_yuvp_pack) and the window kernels behind the packed rect call
-// (srcnn_yuv_packed_window.hip: k_yuvp_window_y, k_yuvp_window_merge) include it, which is why a rect holds the bytes of the frame.
+// a 16-byte chunk (PkShape), its four dwords <-> field values (decode, encode; luma_field: one luma sample off its one dword), the
+// dword access in pieces of the alignment a frame has (load_dword, store_dword; io_of is srcnn_frame_rules.h) and the float ->
+// field conversion of the pack side (to_word).  The whole-frame kernels (srcnn_yuv_packed.hip: k_yuvp_unpack, k_yuvp_pack), the
+// window kernels behind the packed rect call (srcnn_yuv_packed_window.hip: k_yuvp_window_y, k_yuvp_window_merge) and the kernels
+// of the packed rect list call (srcnn_yuv_packed_rect_list.hip) include it, which is why a rect holds the bytes of the frame.
 // Everything has internal linkage, as it had inside srcnn_yuv_packed.hip.  Internal, HIP only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,8 +27,7 @@ template <> struct PkShape<kPk410>    { static constexpr unsigned NY = 4, NC = 4
 template <> struct PkShape<kPk444x16> { static constexpr unsigned NY = 2, NC = 2, NA = 2; };
 template <> struct PkShape<kPkV210>   { static constexpr unsigned NY = 6, NC = 3, NA = 0; };
 
-// how the packed side of a launch is addressed: 16-byte vectors, or pieces of 4, 2 or 1 bytes
-enum { kIoVec = 0, kIoDword = 4, kIoWord = 2, kIoByte = 1 };
+// (kIoVec / kIoDword / kIoWord / kIoByte and io_of: srcnn_frame_rules.h, which the host-only route code shares)
 
 template <bool SAT>
 __device__ __forceinline__ unsigned to_word(float v, float scale, float maxv)
@@ -98,6 +98,29 @@ __device__ __forceinline__ void decode(const unsigned q[4], const YuvPackedRule&
     }
 }
 
+// The luma field of pixel x of a packed row, as decode<K> gives it, from the ONE dword of the row that holds it (in pieces of
+// `io`): the other dwords of the pixel's unit are not loaded.
+template <int K>
+__device__ __forceinline__ unsigned luma_field(const unsigned char* row, size_t x, const YuvPackedRule& f, int io)
+{
+    if constexpr (K == kPk422x8) {
+        return (load_dword(row + 4 * (x / 2), io) >> ((x & 1) ? f.sh[2] : f.sh[0])) & 0xffu;
+    } else if constexpr (K == kPk422x16) {
+        return ((load_dword(row + 4 * x, io) & 0xffffu) >> f.shift) & f.mask;
+    } else if constexpr (K == kPk444x8) {
+        return (load_dword(row + 4 * x, io) >> f.sh[0]) & 0xffu;
+    } else if constexpr (K == kPk410) {
+        return (load_dword(row + 4 * x, io) >> 10) & 0x3ffu;
+    } else if constexpr (K == kPk444x16) {
+        return load_dword(row + 8 * x, io) >> 16;
+    } else {                             // v210: Y0 in dword 0, Y1 Y2 in 1, Y3 in 2, Y4 Y5 in 3
+        const unsigned k = (unsigned)(x % 6);
+        const unsigned dw = (k + 1) / 2 + (k == 4 ? 1u : 0u);                        // 0 1 1 2 3 3
+        const unsigned sh = (k == 0 || k == 3) ? 10u : ((k == 1 || k == 4) ? 0u : 20u);
+        return (load_dword(row + 16 * (x / 6) + 4 * dw, io) >> sh) & 0x3ffu;
+    }
+}
+
 // field values (already inside their fields' ranges; zero where the slot carries no sample) -> the four dwords of a chunk
 template <int K>
 __device__ __forceinline__ void encode(const unsigned* y, const unsigned* u, const unsigned* v, const unsigned* a, const YuvPackedRule& f, unsigned q[4])
@@ -129,12 +152,6 @@ __device__ __forceinline__ void encode(const unsigned* y, const unsigned* u, con
         q[2] = v[1] | (y[3] << 10) | (u[2] << 20);
         q[3] = y[4] | (v[2] << 10) | (y[5] << 20);
     }
-}
-
-inline int io_of(const void* base, size_t pitch)
-{
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(base) | (uintptr_t)pitch;
-    return bits % 16 == 0 ? kIoVec : bits % 4 == 0 ? kIoDword : bits % 2 == 0 ? kIoWord : kIoByte;
 }
 
 }  // namespace
