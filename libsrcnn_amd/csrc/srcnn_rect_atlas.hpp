@@ -157,19 +157,8 @@ inline void pack_rect_cells(RectListRoute& route, unsigned long long cap_bytes)
     }
 }
 
-// The whole decision for a list: who goes which way, and where the batched cells lie.
-inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteInputs& in)
-{
-    RectListRoute route;
-    for (unsigned k = 0; k < n; ++k) {
-        if (rect_item_batched(r[k], in)) route.cells.push_back(AtlasCell{k, 0, 0, 0, r[k].rw + 2 * kCellMargin, r[k].rh + 2 * kCellMargin});
-        else route.single.push_back(k);
-    }
-    pack_rect_cells(route, in.cap_bytes);
-    return route;
-}
-
-// The same with one more condition on a batched item: extra(rect) (the colour shells of srcnn_rgb_rect_atlas.hpp and srcnn_yuv_rect_atlas.hpp)
+// The whole decision for a list: who goes which way, and where the batched cells lie.  extra(rect): one more condition on a
+// batched item (the colour shells of srcnn_rgb_rect_atlas.hpp, srcnn_yuv_rect_atlas.hpp and srcnn_yuv_packed_rect_atlas.hpp)
 template <class Extra>
 inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteInputs& in, Extra extra)
 {
@@ -180,6 +169,10 @@ inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteI
     }
     pack_rect_cells(route, in.cap_bytes);
     return route;
+}
+inline RectListRoute route_rect_list(const ListRect* r, unsigned n, const RouteInputs& in)
+{
+    return route_rect_list(r, n, in, [](const ListRect&) { return true; });
 }
 
 // ---- what the kernels of srcnn_rect_list.hip read: one descriptor per cell of a pass, and one closing entry that holds the totals ----
@@ -228,5 +221,27 @@ inline bool build_cell_descs(const RectListRoute& route, const AtlasPass& pass, 
     end.rs_tile0 = (unsigned)rs; end.rep_tile0 = (unsigned)rep; end.sc_tile0 = (unsigned)sc;
     return true;
 }
+
+// ---- where the tables of a batched list lie, in the staging slot on the host and in Workspace::list on the device alike ----
+// The cell tables of every pass (count + 1 entries each), then -- for a list that has a second table -- the destination tables
+// of every pass: count entries each, and a closing one where the surface's kernels want a total (dst_closing == 1).  The passes
+// of a route follow each other in `cells`, so the first entry of pass k is its `first` plus the closing entries ahead of it.
+struct ListTableLayout {
+    size_t dst_entry_bytes;             // 0: no destination table (the Y list)
+    unsigned dst_closing;               // 0 / 1 closing entries per pass of the destination table
+    size_t dst_offset;                  // bytes of the cell tables = where the destination tables begin (80 is a multiple of 8)
+    size_t bytes;                       // both tables
+    ListTableLayout(const RectListRoute& route, size_t dst_entry_bytes_, unsigned dst_closing_)
+        : dst_entry_bytes(dst_entry_bytes_), dst_closing(dst_closing_), dst_offset((route.cells.size() + route.passes.size()) * sizeof(ListCellDesc)),
+          bytes(dst_offset + (dst_entry_bytes_ ? (route.cells.size() + route.passes.size() * dst_closing_) * dst_entry_bytes_ : 0))
+    {
+    }
+    size_t cell_first(const RectListRoute& route, size_t k) const { return route.passes[k].first + k; }
+    size_t dst_first(const RectListRoute& route, size_t k) const { return route.passes[k].first + k * dst_closing; }
+    // the tables of pass k in a buffer that begins at `base`
+    ListCellDesc* cells(unsigned char* base, const RectListRoute& route, size_t k) const { return reinterpret_cast<ListCellDesc*>(base) + cell_first(route, k); }
+    template <class Dst>
+    Dst* dsts(unsigned char* base, const RectListRoute& route, size_t k) const { return reinterpret_cast<Dst*>(base + dst_offset) + dst_first(route, k); }
+};
 
 }  // namespace srcnn

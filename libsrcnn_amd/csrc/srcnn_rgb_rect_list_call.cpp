@@ -1,17 +1,12 @@
-// srcnn_rgb_rect_list_call.cpp -- the RGB(A) rect LIST call (include/srcnn_amd_rgb_rect_list.h): argument checks, routing and
-// packing (srcnn_rect_atlas.hpp with the chroma condition of srcnn_rgb_rect_atlas.hpp), the upload of the two descriptor tables
-// and the six launches of an atlas (srcnn_rgb_rect_list.hip around the list's replicate and the unchanged layer kernels).  Single
-// items go through rgb_rect of srcnn_frames.cpp, exactly as the single call runs it.
-#include <algorithm>
-#include <cstring>
-#include <string>
+// srcnn_rgb_rect_list_call.cpp -- the RGB(A) rect LIST call (include/srcnn_amd_rgb_rect_list.h): its argument checks, the chroma
+// condition of srcnn_rgb_rect_atlas.hpp on the route, and what RGB(A) adds to the list skeleton (srcnn_rect_list_call.hpp:
+// the descriptor upload and the launches of an atlas): the destination table and the resample and merge of
+// srcnn_rgb_rect_list.hip.  Single items go through rgb_rect of srcnn_frames.cpp, exactly as the single call runs it.
 #include <vector>
 
 #include "../../include/srcnn_amd_rgb_rect_list.h"
-#include "resample_table.hpp"
 #include "srcnn_frame_args.hpp"
-#include "srcnn_host.hpp"
-#include "srcnn_rect_list.h"
+#include "srcnn_rect_list_call.hpp"
 #include "srcnn_rect_source.hpp"
 #include "srcnn_rgb.h"
 #include "srcnn_rgb_rect_atlas.hpp"
@@ -23,44 +18,25 @@ namespace {
 static_assert(sizeof(srcnn_rgb_rect_item) == 96 || sizeof(void*) != 8, "the header states 96 B per item on LP64");
 static_assert(sizeof(ListCellDesc) == 80 && sizeof(ListDstDesc) == 88, "the header states 80 + 88 B per batched item");
 
-// the failure of item k, with the index in front of what the single call would have said
-int fail_item(int rc, unsigned k)
-{
-    const std::string why = last_error();
-    return fail(rc, "item %u: %s", k, why.c_str());
-}
-
-// What both entry points refuse about the list itself.  SRCNN_OK with n == 0: nothing to do.
 int check_list(const srcnn_rgb_rect_item* items, unsigned n, unsigned item_size)
 {
-    if (item_size != sizeof(srcnn_rgb_rect_item))
-        return fail(SRCNN_E_ARG, "item_size %u is not sizeof(srcnn_rgb_rect_item) = %zu", item_size, sizeof(srcnn_rgb_rect_item));
-    if (n == 0) return SRCNN_OK;
-    if (!items) return fail(SRCNN_E_ARG, "NULL items with n = %u", n);
-    if (n > kRectListMax) return fail(SRCNN_E_UNSUPPORTED, "%u items: a list holds at most %u", n, kRectListMax);
-    return SRCNN_OK;
+    return check_list_header(items, n, item_size, sizeof(srcnn_rgb_rect_item), "srcnn_rgb_rect_item");
 }
 
-RgbRouteInputs route_inputs(unsigned w, unsigned h, unsigned dw, unsigned dh, int mode, bool foreign_capture)
+RgbRouteInputs route_inputs(unsigned w, unsigned h, unsigned dw, unsigned dh, int mode, bool foreign)
 {
     RgbRouteInputs in;
-    in.y.w = w; in.y.h = h; in.y.dw = dw; in.y.dh = dh;
-    in.y.strict = mode == SRCNN_MODE_STRICT;
-    in.y.unfused = foreign_capture || settings().rgb_rect_list_unfused;
-    in.y.cap_bytes = G.ws_budget.load();
-    in.y.single_samples = settings().rect_list_single_samples > 0 ? (unsigned long long)settings().rect_list_single_samples : 0;
+    in.y = list_route_inputs(w, h, dw, dh, mode, foreign || settings().rgb_rect_list_unfused);
     return in;
 }
-bool may_batch(const RgbRouteInputs& in) { return in.y.strict && !in.y.unfused && in.y.dw > in.y.w && in.y.dh > in.y.h; }
+bool may_batch(const RgbRouteInputs& in) { return list_may_batch(in.y); }
 
-unsigned long long largest_atlas(const RectListRoute& route)
+// Y: (dw <- w), (dh <- h); chroma: the same axes with chroma_filter
+ListAxes list_axes(int filter, unsigned w, unsigned h, unsigned dw, unsigned dh)
 {
-    unsigned long long largest = 0;
-    for (const AtlasPass& p : route.passes) largest = std::max(largest, (unsigned long long)p.W * p.H);
-    return largest;
+    const int cfilter = chroma_filter(filter);
+    return ListAxes{{filter, dw, w}, {filter, dh, h}, {cfilter, dw, w}, {cfilter, dh, h}};
 }
-
-struct Tables { TableRef th, tv, cth, ctv; };       // Y: (dw <- w), (dh <- h); chroma: the same axes with chroma_filter
 
 struct Source {
     const RgbRule& g;
@@ -69,83 +45,31 @@ struct Source {
     unsigned w, h;
 };
 
-// One atlas: the six launches.  d / dd: the device copies of the pass's cell and destination tables, hd: the host copy of d.
-int list_pass(Call& c, const Source& s, const Tables& t, const AtlasPass& pass, const ListCellDesc* d, const ListDstDesc* dd, const ListCellDesc* hd)
-{
-    Workspace& ws = *c.ws;
-    const ListCellDesc& end = hd[pass.count];
-    const unsigned W = pass.W, H = pass.H;
-    const size_t plane = (size_t)W * H;
-    TraceRange tr("srcnn rgb rect list atlas %ux%u, %u cells", W, H, pass.count);
+// RGB(A) in the skeleton: one ListDstDesc per cell, Y' read by k_rgb_list_resample, colour resampled and merged by k_rgb_list_merge
+struct Shell {
+    using Dst = ListDstDesc;
+    static constexpr unsigned kDstClosing = 0;
+    static constexpr const char* kTrace = "srcnn rgb rect list";
+    static constexpr const char* kName = "rgb_upscale_rect_list";
+    const Source& s;
+    const Tables& t;
+    const RgbListLayout& lay;
+    const RgbListDst* dsts;
+    const ListOut* outs() const { return nullptr; }
+    bool build_dst(const RectListRoute& route, const AtlasPass& pass, const ListRect*, std::vector<Dst>& d) const
     {
-        StageTimer st(SRCNN_STAGE_RESAMPLE, c);
-        launch_rgb_list_resample(s.g, s.src, s.spitch, s.w, s.h, t.th->view(), t.tv->view(), d, pass.count, end, ws.up.data(), W, c.s);
-        launch_list_replicate(d, pass.count, end, ws.up.data(), W, 0, 1, kCellMargin, c.s);
+        build_dst_descs(route, pass, dsts, lay, d);
+        return true;
     }
+    void fill(Call& c, const ListPass<Dst>& p) const
     {
-        StageTimer st(SRCNN_STAGE_CONV12, c);
-        run_conv12(c, ws.up.data(), (int)W, (int)H, 0, (int)H, ws.c2.data(), plane, 0, (int)H);
+        launch_rgb_list_resample(s.g, s.src, s.spitch, s.w, s.h, t.th->view(), t.tv->view(), p.d, p.count, p.end, c.ws->up.data(), p.W, c.s);
     }
+    void store(Call& c, const ListPass<Dst>& p) const
     {
-        StageTimer st(SRCNN_STAGE_CONV3, c);
-        // (the ring of 2 of layer-2 activations around a rect that lies outside the plane: as in the Y list)
-        launch_list_replicate(d, pass.count, end, ws.c2.data(), W, plane, C2N, 2, c.s);
-        launch_layer3(ws.c2.data(), plane, (int)W, (int)H, 0, (int)H, ws.win.data(), 0, (int)H, c.relax(), c.s);
+        launch_rgb_list_merge(s.g, s.src, s.spitch, s.w, s.h, t.cth->view(), t.ctv->view(), p.d, p.dd, p.count, p.end, c.ws->win.data(), p.W, c.s);
     }
-    launch_rgb_list_merge(s.g, s.src, s.spitch, s.w, s.h, t.cth->view(), t.ctv->view(), d, dd, pass.count, end, ws.win.data(), W, c.s);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-        ws.queue_dirty = true;
-        return fail(SRCNN_E_HIP, "rgb_upscale_rect_list: %s", hipGetErrorString(e));
-    }
-    return SRCNN_OK;
-}
-
-// The batched route: the cell tables of every pass, then the destination tables of every pass, go to the device in ONE copy, in
-// stream order, from a page-locked slot that belongs to this call until its event has passed (ListStaging, srcnn_host.hpp).
-int list_batched(Call& c, const Source& s, const RgbListLayout& lay, unsigned dw, unsigned dh, const Tables& t, const RectListRoute& route,
-                 const ListRect* rects, const RgbListDst* dsts)
-{
-    Workspace& ws = *c.ws;
-    int rc;
-    const size_t cell_entries = route.cells.size() + route.passes.size();
-    const size_t cell_bytes = cell_entries * sizeof(ListCellDesc), bytes = (size_t)rgb_list_desc_bytes(route);
-    // all scratch first: growing drains the device, which nothing queued below may see half way
-    const size_t largest = (size_t)largest_atlas(route);
-    if ((rc = ws.grow(ws.up, largest)) || (rc = ws.grow(ws.win, largest)) || (rc = ws.grow(ws.c2, (size_t)C2N * largest)) || (rc = ws.grow(ws.list, bytes))) return rc;
-    ListStaging::Slot& slot = ws.list_stage.slot[ws.list_stage.next];
-    ws.list_stage.next = (ws.list_stage.next + 1) % ListStaging::kSlots;
-    if (slot.pending) {
-        if (wait_event(slot.ev.get()) != hipSuccess) return fail(SRCNN_E_HIP, "an earlier descriptor upload of this stream failed");
-        slot.pending = false;
-    }
-    if ((rc = slot.pin.grow(bytes, *c.cx))) return rc;
-    if (!slot.ev) HIP_TRY(hipEventCreateWithFlags(slot.ev.put(), hipEventDisableTiming));
-    ListCellDesc* host = reinterpret_cast<ListCellDesc*>(slot.pin.data());
-    ListDstDesc* host_dst = reinterpret_cast<ListDstDesc*>(slot.pin.data() + cell_bytes);        // (80 and 88 are multiples of 8)
-    std::vector<ListCellDesc> one;
-    std::vector<ListDstDesc> one_dst;
-    std::vector<size_t> at, at_dst;                // first entry of each pass in the two tables
-    size_t pos = 0, pos_dst = 0;
-    for (const AtlasPass& p : route.passes) {
-        if (!build_cell_descs(route, p, rects, nullptr, dw, dh, one) || one.back().rs_tile0 > 0x7fffffffu || one.back().rep_tile0 > 0x7fffffffu ||
-            one.back().sc_tile0 > 0x7fffffffu)
-            return fail(SRCNN_E_UNSUPPORTED, "an atlas of %u cells has more tiles than one launch takes", p.count);
-        build_dst_descs(route, p, dsts, lay, one_dst);
-        memcpy(host + pos, one.data(), one.size() * sizeof(ListCellDesc));
-        memcpy(host_dst + pos_dst, one_dst.data(), one_dst.size() * sizeof(ListDstDesc));
-        at.push_back(pos); at_dst.push_back(pos_dst);
-        pos += one.size(); pos_dst += one_dst.size();
-    }
-    unsigned char* dev = ws.list.data();
-    HIP_TRY(hipMemcpyAsync(dev, slot.pin.data(), bytes, hipMemcpyHostToDevice, c.s));
-    HIP_TRY(hipEventRecord(slot.ev.get(), c.s));
-    slot.pending = true;
-    const ListCellDesc* dev_cells = reinterpret_cast<const ListCellDesc*>(dev);
-    const ListDstDesc* dev_dst = reinterpret_cast<const ListDstDesc*>(dev + cell_bytes);
-    for (size_t k = 0; k < route.passes.size(); ++k)
-        if ((rc = list_pass(c, s, t, route.passes[k], dev_cells + at[k], dev_dst + at_dst[k], host + at[k]))) return rc;
-    return SRCNN_OK;
-}
+};
 
 }  // namespace
 
@@ -157,13 +81,9 @@ int srcnn_rgb_upscale_rect_list_plan(const srcnn_rgb_format* fmt, unsigned w, un
                                      const srcnn_rgb_rect_item* items, unsigned n, unsigned item_size, srcnn_rect_list_plan* plan)
 {
     int rc;
-    if (!plan) return fail(SRCNN_E_ARG, "NULL plan");
-    if (plan->struct_size != sizeof(srcnn_rect_list_plan))
-        return fail(SRCNN_E_ARG, "plan->struct_size %u is not sizeof(srcnn_rect_list_plan) = %zu", plan->struct_size, sizeof(srcnn_rect_list_plan));
+    if ((rc = check_plan(plan))) return rc;
     if ((rc = check_list(items, n, item_size))) return rc;
-    srcnn_rect_list_plan out{};
-    out.struct_size = (unsigned)sizeof(srcnn_rect_list_plan);
-    if (n == 0) { *plan = out; return SRCNN_OK; }
+    if (n == 0) { fill_plan(plan, RectListRoute{}, 0); return SRCNN_OK; }
     RgbRule g;
     unsigned dw = 0, dh = 0;
     if ((rc = rgb_rule_from_format(fmt, g))) return rc;
@@ -175,26 +95,13 @@ int srcnn_rgb_upscale_rect_list_plan(const srcnn_rgb_format* fmt, unsigned w, un
         rects[k] = ListRect{it.x0, it.y0, it.rw, it.rh};
     }
     RgbRouteInputs in = route_inputs(w, h, dw, dh, G.mode.load(), false);
-    AxisTable th, tv, cth, ctv;
+    PlanTables t;
     if (may_batch(in)) {
-        const int cfilter = chroma_filter(filter);
-        th = build_axis_table(filter, dw, w);
-        tv = build_axis_table(filter, dh, h);
-        cth = build_axis_table(cfilter, dw, w);
-        ctv = build_axis_table(cfilter, dh, h);
-        in.y.th = TileAxis{th.first.data(), th.taps.data(), th.max_taps};
-        in.y.tv = TileAxis{tv.first.data(), tv.taps.data(), tv.max_taps};
-        in.cth = TileAxis{cth.first.data(), cth.taps.data(), cth.max_taps};
-        in.ctv = TileAxis{ctv.first.data(), ctv.taps.data(), ctv.max_taps};
+        build_tables(list_axes(filter, w, h, dw, dh), t);
+        set_tile_axes(in, t);
     }
     const RectListRoute route = route_rgb_rect_list(rects.data(), n, in);
-    out.batched_items = (unsigned)route.cells.size();
-    out.single_items = (unsigned)route.single.size();
-    out.atlases = (unsigned)route.passes.size();
-    out.cell_samples = route.cell_samples;
-    out.atlas_samples = route.atlas_samples;
-    out.scratch_bytes = largest_atlas(route) * (kAtlasSampleBytes + 8) + rgb_list_desc_bytes(route);
-    *plan = out;
+    fill_plan(plan, route, rgb_list_desc_bytes(route));
     return SRCNN_OK;
 }
 
@@ -239,25 +146,17 @@ int srcnn_rgb_upscale_rect_list_dev(const srcnn_rgb_format* fmt, unsigned w, uns
     StreamCall sc(stream);
     if (sc.rc) return sc.rc;
     Call& c = sc.c;
-    // a capture that is not the library's own, as run_conv12 detects it: the descriptor upload and the tile queue stay out of it
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool foreign_capture = c.s && c.ws && !c.ws->frozen && hipStreamIsCapturing(c.s, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive;
-    RgbRouteInputs ri = route_inputs(w, h, dw, dh, c.mode, foreign_capture);
+    RgbRouteInputs ri = route_inputs(w, h, dw, dh, c.mode, foreign_capture(c));
     Tables t;
     if (may_batch(ri)) {
-        const int cfilter = chroma_filter(filter);
-        if ((rc = get_table(c, filter, dw, w, t.th)) || (rc = get_table(c, filter, dh, h, t.tv)) || (rc = get_table(c, cfilter, dw, w, t.cth)) ||
-            (rc = get_table(c, cfilter, dh, h, t.ctv)))
-            return rc;
-        ri.y.th = TileAxis{t.th->h_first.data(), t.th->h_taps.data(), t.th->max_taps};
-        ri.y.tv = TileAxis{t.tv->h_first.data(), t.tv->h_taps.data(), t.tv->max_taps};
-        ri.cth = TileAxis{t.cth->h_first.data(), t.cth->h_taps.data(), t.cth->max_taps};
-        ri.ctv = TileAxis{t.ctv->h_first.data(), t.ctv->h_taps.data(), t.ctv->max_taps};
+        if ((rc = get_tables(c, list_axes(filter, w, h, dw, dh), t))) return rc;
+        set_tile_axes(ri, t);
     }
     const RectListRoute route = route_rgb_rect_list(rects.data(), n, ri);
     Source s{g, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, w, h};
     for (int k = 0; k < np; ++k) { s.src[k] = in[k].lo; s.spitch[k] = in[k].pitch; }
-    if (!route.cells.empty() && (rc = list_batched(c, s, lay, dw, dh, t, route, rects.data(), dsts.data()))) return rc;
+    const Shell sh{s, t, lay, dsts.data()};
+    if (!route.cells.empty() && (rc = list_batched(c, sh, dw, dh, route, rects.data()))) return rc;
     for (unsigned k : route.single) {
         const ListRect& r = rects[k];
         const RgbListDst& q = dsts[k];

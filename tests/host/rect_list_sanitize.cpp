@@ -10,7 +10,9 @@
 //     checked it against the cap) and the Y path's limits;
 //   * cells are pairwise disjoint (every atlas sample is painted at most once);
 //   * the tile prefix sums of a pass start at 0, grow by exactly the tiles of each cell, and end in the closing entry;
-//   * the in-plane part of a cell lies inside the cell and inside the plane, and the same list packs the same way twice.
+//   * the in-plane part of a cell lies inside the cell and inside the plane, and the same list packs the same way twice;
+//   * the staging buffer filled through ListTableLayout is the tables of the passes one after another, every byte of it belongs
+//     to exactly one pass, and it has the bytes the plan call reports for the tables.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,6 +73,32 @@ static ListRect random_rect(Rng& g, const Frame& f, unsigned max_side)
     return r;
 }
 
+// The staging buffer as the batched route fills it (list_batched, srcnn_rect_list_call.hpp): every pass's table copied to where
+// ListTableLayout puts it.  `all`: the tables of the passes one after another, as check_route has built and checked them.
+static void check_layout(const char* what, const RectListRoute& route, const std::vector<ListRect>& rects, const std::vector<ListOut>& outs, const Frame& f,
+                         const std::vector<ListCellDesc>& all)
+{
+    const ListTableLayout lay(route, 0, 0);        // the Y list: one table
+    std::vector<unsigned char> buf(lay.bytes, 0xa5), writes(lay.bytes, 0);
+    std::vector<ListCellDesc> d;
+    for (size_t k = 0; k < route.passes.size(); ++k) {
+        if (!build_cell_descs(route, route.passes[k], rects.data(), outs.data(), f.dw, f.dh, d)) return;      // (check_route has said so)
+        const size_t at = lay.cell_first(route, k) * sizeof(ListCellDesc), n = d.size() * sizeof(ListCellDesc);
+        CHECK(at + n <= lay.bytes, "%s: the table of pass %zu ends at byte %zu of %zu", what, k, at + n, lay.bytes);
+        if (at + n > lay.bytes) return;
+        std::copy(d.begin(), d.end(), lay.cells(buf.data(), route, k));
+        for (size_t b = at; b < at + n; ++b) ++writes[b];
+    }
+    size_t holes = 0, twice = 0;
+    for (unsigned char w : writes) { holes += w == 0; twice += w > 1; }
+    CHECK(holes == 0 && twice == 0, "%s: %zu bytes of the staging buffer belong to no pass, %zu to two", what, holes, twice);
+    CHECK(lay.bytes == all.size() * sizeof(ListCellDesc) && (lay.bytes == 0 || std::memcmp(buf.data(), all.data(), lay.bytes) == 0),
+          "%s: the staging buffer (%zu bytes) is not the tables of the passes one after another (%zu entries)", what, lay.bytes, all.size());
+    // what srcnn_y_path_rect_list_plan counts beside the atlas: a cell entry per batched item and the closing entry of every atlas
+    CHECK(lay.dst_offset == lay.bytes && lay.bytes == (route.cells.size() + route.passes.size()) * sizeof(ListCellDesc), "%s: %zu bytes of tables for %zu cells in %zu passes",
+          what, lay.bytes, route.cells.size(), route.passes.size());
+}
+
 static void check_route(const char* what, const Frame& f, const std::vector<ListRect>& rects, const RouteInputs& in, unsigned want_min_passes)
 {
     const unsigned n = (unsigned)rects.size();
@@ -86,7 +114,7 @@ static void check_route(const char* what, const Frame& f, const std::vector<List
     size_t next = 0;
     std::vector<ListOut> outs(n);
     for (unsigned k = 0; k < n; ++k) outs[k] = ListOut{reinterpret_cast<void*>((uintptr_t)0x1000 + 16u * k), rects[k].rw};
-    std::vector<ListCellDesc> d;
+    std::vector<ListCellDesc> d, all;       // all: the tables of every pass, one after another
     for (size_t p = 0; p < route.passes.size(); ++p) {
         const AtlasPass& a = route.passes[p];
         CHECK(a.first == next && a.count > 0 && a.first + (size_t)a.count <= route.cells.size(), "%s: pass %zu covers [%u, +%u)", what, p, a.first, a.count);
@@ -137,7 +165,9 @@ static void check_route(const char* what, const Frame& f, const std::vector<List
             sc += (unsigned long long)((e.rw + 63) / 64) * ((e.rh + 15) / 16);
         }
         CHECK(d[a.count].rs_tile0 == rs && d[a.count].rep_tile0 == rep && d[a.count].sc_tile0 == sc, "%s: closing entry of pass %zu", what, p);
+        all.insert(all.end(), d.begin(), d.end());
     }
+    check_layout(what, route, rects, outs, f, all);
     CHECK(next == route.cells.size(), "%s: %zu cells, passes cover %zu", what, route.cells.size(), next);
     for (unsigned k = 0; k < n; ++k) CHECK(seen[k], "%s: item %u is nowhere", what, k);
     CHECK(cell_sum == route.cell_samples && atlas_sum == route.atlas_samples, "%s: sums", what);

@@ -13,7 +13,10 @@
 //     as the kernels walk them -- are exactly the item's rows at its pitches, plane by plane;
 //   * a vector flag is set only where every base and pitch it covers is a multiple of the store size (and is set where they are);
 //   * an item whose chroma window does not fit the tile resampler is routed single, whatever the Y list says about it;
-//   * a frame whose chroma axis keeps its size while luma grows routes every item single.
+//   * a frame whose chroma axis keeps its size while luma grows routes every item single;
+//   * the staging buffer filled through ListTableLayout (srcnn_rect_atlas.hpp) is the cell tables of the passes and then their
+//     destination tables, closing entries included, every byte of it belongs to exactly one table, and it has the bytes the plan
+//     call reports for the tables.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -199,6 +202,43 @@ static void paint_chroma(const YuvListDstDesc& o, unsigned next_tile0, const Yuv
 
 struct Tally { size_t lvec = 0, lscalar = 0, cvec = 0, cscalar = 0; };
 
+// The staging buffer as the batched route fills it (list_batched, srcnn_rect_list_call.hpp): both tables of every pass copied to
+// where ListTableLayout puts them -- two tables, each with a closing entry per pass.  all_cells / all_dst: the tables of the
+// passes one after another, as check_list has built and checked them.
+static void check_layout(const char* what, const Frame& fr, const RectListRoute& route, const std::vector<ListRect>& rects, const Arena& a,
+                         const std::vector<ListCellDesc>& all_cells, const std::vector<YuvListDstDesc>& all_dst)
+{
+    const ListTableLayout lay(route, sizeof(YuvListDstDesc), 1);
+    std::vector<unsigned char> buf(lay.bytes, 0xa5), writes(lay.bytes, 0);
+    std::vector<ListCellDesc> d;
+    std::vector<YuvListDstDesc> dd;
+    for (size_t k = 0; k < route.passes.size(); ++k) {
+        const AtlasPass& pass = route.passes[k];
+        if (!build_cell_descs(route, pass, rects.data(), nullptr, fr.dw, fr.dh, d) || !build_yuv_dst_descs(route, pass, rects.data(), a.dst.data(), fr.g, dd))
+            return;                                                                                  // (check_list has said so)
+        const size_t at = lay.cell_first(route, k) * sizeof(ListCellDesc), n = d.size() * sizeof(ListCellDesc);
+        const size_t at_dst = lay.dst_offset + lay.dst_first(route, k) * sizeof(YuvListDstDesc), n_dst = dd.size() * sizeof(YuvListDstDesc);
+        CHECK(at + n <= lay.dst_offset && at_dst + n_dst <= lay.bytes, "%s: the tables of pass %zu end at bytes %zu of %zu and %zu of %zu", what, k, at + n,
+              lay.dst_offset, at_dst + n_dst, lay.bytes);
+        if (at + n > lay.dst_offset || at_dst + n_dst > lay.bytes) return;
+        std::copy(d.begin(), d.end(), lay.cells(buf.data(), route, k));
+        std::copy(dd.begin(), dd.end(), lay.dsts<YuvListDstDesc>(buf.data(), route, k));
+        for (size_t b = at; b < at + n; ++b) ++writes[b];
+        for (size_t b = at_dst; b < at_dst + n_dst; ++b) ++writes[b];
+    }
+    size_t holes = 0, twice = 0;
+    for (unsigned char w : writes) { holes += w == 0; twice += w > 1; }
+    CHECK(holes == 0 && twice == 0, "%s: %zu bytes of the staging buffer belong to no table, %zu to two", what, holes, twice);
+    const size_t cell_bytes = all_cells.size() * sizeof(ListCellDesc), dst_bytes = all_dst.size() * sizeof(YuvListDstDesc);
+    CHECK(lay.dst_offset == cell_bytes && lay.bytes == cell_bytes + dst_bytes, "%s: %zu + %zu bytes of tables, the layout has %zu + %zu", what, cell_bytes, dst_bytes,
+          lay.dst_offset, lay.bytes - lay.dst_offset);
+    if (lay.dst_offset == cell_bytes && lay.bytes == cell_bytes + dst_bytes && lay.bytes)
+        CHECK(std::memcmp(buf.data(), all_cells.data(), cell_bytes) == 0 && std::memcmp(buf.data() + cell_bytes, all_dst.data(), dst_bytes) == 0,
+              "%s: the staging buffer is not the cell tables of the passes and then their destination tables", what);
+    // what srcnn_yuv_upscale_rect_list_plan counts beside the atlas
+    CHECK(lay.bytes == yuv_list_desc_bytes(route), "%s: the layout has %zu bytes, the plan reports %llu", what, lay.bytes, yuv_list_desc_bytes(route));
+}
+
 static void check_list(const char* what, const Frame& fr, const std::vector<ListRect>& rects, const YuvRouteInputs& in, Rng& g, bool expect_all_batched,
                        Tally& tally)
 {
@@ -208,8 +248,8 @@ static void check_list(const char* what, const Frame& fr, const std::vector<List
     const RectListRoute route = route_yuv_rect_list(rects.data(), n, in);
     if (expect_all_batched) CHECK(route.single.empty(), "%s: %zu items single", what, route.single.size());
     std::vector<unsigned char> owner(n, 0), paint(a.bytes, 0), want(a.bytes, 0);
-    std::vector<ListCellDesc> d;
-    std::vector<YuvListDstDesc> dd;
+    std::vector<ListCellDesc> d, all_cells;          // all_*: the tables of every pass, one after another
+    std::vector<YuvListDstDesc> dd, all_dst;
     const Painter P{a, paint, what};
     size_t entries = 0;
     for (const AtlasPass& pass : route.passes) {
@@ -259,7 +299,10 @@ static void check_list(const char* what, const Frame& fr, const std::vector<List
             }
         }
         CHECK(dd[pass.count].ch_tile0 == tiles, "%s: the closing entry says %u chroma tiles, the items have %llu", what, dd[pass.count].ch_tile0, tiles);
+        all_cells.insert(all_cells.end(), d.begin(), d.end());
+        all_dst.insert(all_dst.end(), dd.begin(), dd.end());
     }
+    check_layout(what, fr, route, rects, a, all_cells, all_dst);
     CHECK(entries == route.cells.size(), "%s: %zu destination entries for %zu cells", what, entries, route.cells.size());
     for (unsigned k : route.single) { CHECK(k < n && !owner[k], "%s: single item %u has a destination entry", what, k); if (k < n) owner[k] = 2; }
     for (unsigned k = 0; k < n; ++k) CHECK(owner[k], "%s: item %u is nowhere", what, k);

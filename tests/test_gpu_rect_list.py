@@ -176,6 +176,91 @@ def test_two_lists_back_to_back_on_one_stream(srcnn, frame):
         st.destroy()
 
 
+# ---- six calls of the four surfaces back to back: the staging ring of the stream wraps ----
+RING_FRAME = (48, 36, 96, 72)
+
+
+def ring_rects(k):
+    """The list of call k: a rect at the origin corner, one that touches the far corner and an interior one, none larger than
+    24 x 16, origins and widths even (YUY2's unit, 4:2:0's origin rule), different for every k."""
+    _w, _h, dw, dh = RING_FRAME
+    return [(0, 0, 24 - 2 * k, 16 - 2 * k),
+            (dw - 8 - 2 * k, dh - 6 - 2 * k, 8 + 2 * k, 6 + 2 * k),
+            (20 + 4 * k, 10 + 2 * k, 12 + 2 * k, 15 - k)]
+
+
+def ring_surfaces(S):
+    """Per surface: (rig, layout(rects) -> (lay, bytes), submit(rects, buf, lay, stream), fetch(rects, buf, lay), loop(rects));
+    fetch and loop give one entry per item.  The destination buffers are the caller's, so that nothing but the list calls
+    themselves happens between the first and the last of them."""
+    from rgb_rect_list_worker import RgbListRig
+    from test_gpu_yuv_ex import frame as yuv_frame
+    from test_rgb_restatement import image
+    from yuv_packed_rect_list_worker import PackedListRig, source
+    from yuv_rect_list_worker import YuvListRig
+    w, h, dw, dh = RING_FRAME
+    y = ListRig(S, synth.plane(h, w, synth.SEED0 + 540, "noise"), dw, dh)
+    rgb = RgbListRig(S, image(w, h, 0, 8, 541), "interleaved", "rgb", 8)
+    yuv = YuvListRig(S, *yuv_frame(w, h, "420", 8, 542), "planar", "420", 8, 0, 2.0, 2)
+    pk = PackedListRig(S, "yuy2", source("yuy2", (w, h, 2, 2.0)), w)
+    assert (rgb.dw, rgb.dh) == (dw, dh) and (pk.dw, pk.dh) == (dw, dh)
+
+    def y_submit(rects, buf, offs, st):
+        S.y_path_rect_list_dev(y.din, y.in_pitch, w, h, dw, dh, 2, [(x0, y0, rw, rh, (buf, o), 0) for (x0, y0, rw, rh), o in zip(rects, offs)], st)
+
+    def rgb_submit(rects, buf, offs, st):
+        items = [(x0, y0, rw, rh, rgb.dst_of(buf, oi, rw, rh), None, (buf, oc), 0) for (x0, y0, rw, rh), (oi, oc) in zip(rects, offs)]
+        S.rgb_upscale_rect_list_dev(rgb.fmt, w, h, 2.0, 2, rgb.src, None, items, st)
+
+    def yuv_submit(rects, buf, lay, st):
+        items = [(x0, y0, rw, rh, [(buf, o) for o, _ in one], None) for (x0, y0, rw, rh), one in zip(rects, lay)]
+        S.yuv_upscale_rect_list_dev(yuv.fmt, w, h, 2.0, 2, yuv.din + yuv.pad, None, items, st)
+
+    def pk_submit(rects, buf, offs, st):
+        S.yuv_packed_upscale_rect_list_dev("yuy2", w, h, 2.0, 2, pk.din, 0, pk.items(rects, buf, offs), st)
+
+    return {"y": (y, y.layout, y_submit, y.fetch, y.loop),
+            "rgb": (rgb, rgb.layout_of, rgb_submit, rgb.fetch, rgb.loop),
+            "i420": (yuv, yuv.layout_of, yuv_submit, lambda rects, buf, lay: yuv.fetch_raw(buf, lay), yuv.raw_loop),
+            "yuy2": (pk, pk.layout, pk_submit, pk.fetch, lambda rects: pk.fetch(*pk.loop(rects)))}
+
+
+def test_six_lists_of_four_surfaces_back_to_back_wrap_the_staging_ring(srcnn):
+    """Y, RGB, I420, YUY2, Y, RGB on one stream without a synchronisation in between: the lists share the stream's descriptor
+    table and its ring of four staging slots, so the fifth call takes the first call's slot again and waits for its event.
+    Every item equals the single rect call run afterwards, byte for byte, and every item went the batched route."""
+    S = srcnn
+    prev = S.set_mode(S.MODE_STRICT)
+    st = S.Stream()
+    try:
+        surf = ring_surfaces(S)
+        calls = []
+        for k, name in enumerate(("y", "rgb", "i420", "yuy2", "y", "rgb")):
+            rig, layout, submit, fetch, loop = surf[name]
+            rects = ring_rects(k)
+            assert all(rw <= 24 and rh <= 16 and x0 % 2 == 0 and y0 % 2 == 0 and rw % 2 == 0 for (x0, y0, rw, rh) in rects)
+            p = rig.plan(rects)
+            assert p.batched_items == len(rects) and p.single_items == 0, (k, name, p.batched_items, p.single_items)
+            lay, total = layout(rects)
+            calls.append((name, rects, S.DeviceBuffer.from_numpy(np.full(total, CANARY, np.uint8)), lay))
+        for name, rects, buf, lay in calls:
+            surf[name][2](rects, buf, lay, st)
+        st.sync()
+        for k, (name, rects, buf, lay) in enumerate(calls):
+            _rig, _layout, _submit, fetch, loop = surf[name]
+            got, want = fetch(rects, buf, lay), loop(rects)
+            assert len(got) == len(want) == len(rects)
+            for j, (g, s) in enumerate(zip(got, want)):
+                gs, ss = (g, s) if isinstance(g, (list, tuple)) else ((g,), (s,))
+                assert len(gs) == len(ss)
+                for a, b in zip(gs, ss):
+                    assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), \
+                        "call %d (%s), item %d, rect %r: the list and the single call differ" % (k, name, j, rects[j])
+    finally:
+        st.destroy()
+        S.set_mode(prev)
+
+
 # ---- every filter at 2x ----
 @pytest.mark.parametrize("filt", range(5), ids=FILTER_NAMES)
 def test_every_filter(srcnn, oracle_lib, frame, filt):
