@@ -7,7 +7,8 @@
 #   make install-yuv -> the same + include/srcnn_amd_yuv.h, srcnn_amd_yuv_ex.h, srcnn_amd_yuv_packed.h (the YUV extensions)
 #   make install-rgb -> the same as install + include/srcnn_amd_rgb.h (RGB(A) images in device memory)
 #   make install-rect -> the same as install + include/srcnn_amd_rect.h (one rectangle of the Y path's output)
-#                      and include/srcnn_amd_rect_list.h (a list of them in one call)
+#                      and include/srcnn_amd_rect_list.h (a list of them in one call) and include/srcnn_amd_delta.h (only what
+#                      changed between two frames)
 #   make install-yuv-packed-rect -> the same as install-yuv and install-rect + include/srcnn_amd_yuv_packed_rect.h (one rectangle of
 #                      a packed frame) and include/srcnn_amd_yuv_packed_rect_list.h (a list of them in one call)
 #   make oracle     -> the CPU checker (and oracle/_ref where the reference tree is present)
@@ -33,12 +34,12 @@ endif
 HIPFLAGS := --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -fvisibility=hidden -Wall \
             -Wno-unused-result -Wno-unused-value -Wno-ignored-attributes -D__HIP_PLATFORM_AMD__ $(STRICT_DEF)
 ifeq ($(STRICT_ONLY),1)
-SRCS    := srcnn_kernels.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_rgb_window.hip srcnn_yuv_window.hip srcnn_yuv_packed_window.hip srcnn_window.hip srcnn_rect_list.hip srcnn_rgb_rect_list.hip srcnn_yuv_rect_list.hip srcnn_yuv_packed_rect_list.hip srcnn_rect_list_call.cpp srcnn_rgb_rect_list_call.cpp srcnn_yuv_rect_list_call.cpp srcnn_yuv_packed_rect_list_call.cpp srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_rgb_window.hip srcnn_yuv_window.hip srcnn_yuv_packed_window.hip srcnn_window.hip srcnn_rect_list.hip srcnn_rgb_rect_list.hip srcnn_yuv_rect_list.hip srcnn_yuv_packed_rect_list.hip srcnn_delta.hip srcnn_rect_list_call.cpp srcnn_rgb_rect_list_call.cpp srcnn_yuv_rect_list_call.cpp srcnn_yuv_packed_rect_list_call.cpp srcnn_delta_call.cpp srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 else
-SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_rgb_window.hip srcnn_yuv_window.hip srcnn_yuv_packed_window.hip srcnn_window.hip srcnn_rect_list.hip srcnn_rgb_rect_list.hip srcnn_yuv_rect_list.hip srcnn_yuv_packed_rect_list.hip srcnn_rect_list_call.cpp srcnn_rgb_rect_list_call.cpp srcnn_yuv_rect_list_call.cpp srcnn_yuv_packed_rect_list_call.cpp srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
+SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_rgb_window.hip srcnn_yuv_window.hip srcnn_yuv_packed_window.hip srcnn_window.hip srcnn_rect_list.hip srcnn_rgb_rect_list.hip srcnn_yuv_rect_list.hip srcnn_yuv_packed_rect_list.hip srcnn_delta.hip srcnn_rect_list_call.cpp srcnn_rgb_rect_list_call.cpp srcnn_yuv_rect_list_call.cpp srcnn_yuv_packed_rect_list_call.cpp srcnn_delta_call.cpp srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 endif
 OBJS    := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(basename $(SRCS))))
-HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_window.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_rect_source.hpp $(CSRC)/srcnn_rect_atlas.hpp $(CSRC)/srcnn_rgb_rect_atlas.hpp $(CSRC)/srcnn_yuv_rect_atlas.hpp $(CSRC)/srcnn_yuv_packed_rect_atlas.hpp $(CSRC)/srcnn_yuv_chroma_tile.h $(CSRC)/srcnn_yuv_packed_merge_tile.h $(CSRC)/srcnn_rect_list.h $(CSRC)/srcnn_rect_list_call.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_colour_rules.h $(CSRC)/srcnn_window_tile.h $(CSRC)/srcnn_yuv_packed_fields.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/srcnn_amd_rect.h include/srcnn_amd_rect_list.h include/srcnn_amd_rgb_rect.h include/srcnn_amd_rgb_rect_list.h include/srcnn_amd_yuv_rect.h include/srcnn_amd_yuv_rect_list.h include/srcnn_amd_yuv_packed_rect.h include/srcnn_amd_yuv_packed_rect_list.h include/libsrcnn_dropin.h
+HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_window.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_rect_source.hpp $(CSRC)/srcnn_rect_atlas.hpp $(CSRC)/srcnn_rgb_rect_atlas.hpp $(CSRC)/srcnn_yuv_rect_atlas.hpp $(CSRC)/srcnn_yuv_packed_rect_atlas.hpp $(CSRC)/srcnn_yuv_chroma_tile.h $(CSRC)/srcnn_yuv_packed_merge_tile.h $(CSRC)/srcnn_rect_list.h $(CSRC)/srcnn_rect_list_call.hpp $(CSRC)/srcnn_delta.h $(CSRC)/srcnn_delta.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_colour_rules.h $(CSRC)/srcnn_window_tile.h $(CSRC)/srcnn_yuv_packed_fields.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/srcnn_amd_rect.h include/srcnn_amd_rect_list.h include/srcnn_amd_rgb_rect.h include/srcnn_amd_rgb_rect_list.h include/srcnn_amd_yuv_rect.h include/srcnn_amd_yuv_rect_list.h include/srcnn_amd_yuv_packed_rect.h include/srcnn_amd_yuv_packed_rect_list.h include/srcnn_amd_delta.h include/libsrcnn_dropin.h
 
 PREFIX  ?= /usr/local
 ROCM    ?= /opt/rocm
@@ -187,10 +188,11 @@ install-yuv: install
 install-rgb: install
 	install -m 644 include/srcnn_amd_rgb.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h
 
-# the rect extension headers (include/srcnn_amd_rect.h, include/srcnn_amd_rect_list.h)
+# the rect extension headers (include/srcnn_amd_rect.h, include/srcnn_amd_rect_list.h, include/srcnn_amd_delta.h)
 install-rect: install
 	install -m 644 include/srcnn_amd_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect.h
 	install -m 644 include/srcnn_amd_rect_list.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect_list.h
+	install -m 644 include/srcnn_amd_delta.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_delta.h
 
 # the packed rect extension headers: include/srcnn_amd_yuv_packed_rect.h, which includes srcnn_amd_yuv_packed.h, and
 # include/srcnn_amd_yuv_packed_rect_list.h, which includes that one and srcnn_amd_rect_list.h
@@ -200,7 +202,7 @@ install-yuv-packed-rect: install-yuv install-rect
 
 uninstall:
 	rm -f $(DESTDIR)$(PREFIX)/lib/libsrcnn_amd.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.so $(DESTDIR)$(PREFIX)/lib/libsrcnn.a
-	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect_list.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed_rect_list.h
+	rm -f $(DESTDIR)$(PREFIX)/include/libsrcnn.h $(DESTDIR)$(PREFIX)/include/srcnn_amd.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_ex.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rgb.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_rect_list.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_delta.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed_rect.h $(DESTDIR)$(PREFIX)/include/srcnn_amd_yuv_packed_rect_list.h
 	@if [ -z "$(DESTDIR)" ] && [ "$$(id -u)" = 0 ]; then ldconfig; fi
 
 clean:

@@ -73,7 +73,10 @@ YUV_RECT_LIST_SYMBOLS = ["srcnn_yuv_rect_list_abi_version", "srcnn_yuv_upscale_r
 # a list of rectangles of a packed YUV frame (include/srcnn_amd_yuv_packed_rect_list.h, listed in include/srcnn_amd_yuv_packed_rect_list.abi; its own version)
 YUV_PACKED_RECT_LIST_SYMBOLS = ["srcnn_yuv_packed_rect_list_abi_version", "srcnn_yuv_packed_upscale_rect_list_plan",
                                 "srcnn_yuv_packed_upscale_rect_list_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS   # everything the library exports besides the two C++ symbols
+# only what changed between two Y frames (include/srcnn_amd_delta.h, listed in include/srcnn_amd_delta.abi; its own version)
+DELTA_SYMBOLS = ["srcnn_delta_abi_version", "srcnn_y_path_delta_grid", "srcnn_y_path_delta_flags_dev", "srcnn_y_path_delta_rects",
+                 "srcnn_y_path_delta_f32_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -112,6 +115,12 @@ class RectListPlan(C.Structure):
     """srcnn_rect_list_plan (include/srcnn_amd_rect_list.h)."""
     _fields_ = [("struct_size", C.c_uint), ("batched_items", C.c_uint), ("single_items", C.c_uint), ("atlases", C.c_uint),
                 ("cell_samples", C.c_ulonglong), ("atlas_samples", C.c_ulonglong), ("scratch_bytes", C.c_ulonglong)]
+
+
+class DeltaStats(C.Structure):
+    """srcnn_delta_stats (include/srcnn_amd_delta.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("tiles", C.c_uint), ("dirty_tiles", C.c_uint), ("rects", C.c_uint), ("whole_frame", C.c_uint),
+                ("cell_samples", C.c_ulonglong)]
 
 
 class SrcnnError(RuntimeError):
@@ -223,9 +232,14 @@ def lib():
             "srcnn_yuv_packed_rect_list_abi_version": (i, []),
             "srcnn_yuv_packed_upscale_rect_list_plan": (i, [i, u, u, f, i, vp, u, u, C.POINTER(RectListPlan)]),
             "srcnn_yuv_packed_upscale_rect_list_dev": (i, [i, u, u, f, i, vp, sz, vp, u, u, vp]),
+            "srcnn_delta_abi_version": (i, []),
+            "srcnn_y_path_delta_grid": (i, [u, u, u, u, i, u, u, C.POINTER(u), C.POINTER(u)]),
+            "srcnn_y_path_delta_flags_dev": (i, [vp, sz, vp, sz, u, u, u, u, i, u, u, vp, vp]),
+            "srcnn_y_path_delta_rects": (i, [vp, u, u, u, u, u, u, vp, sz, vp, u, C.POINTER(u)]),
+            "srcnn_y_path_delta_f32_dev": (i, [vp, sz, vp, sz, u, u, u, u, i, u, u, vp, sz, vp, C.POINTER(DeltaStats)]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -546,6 +560,70 @@ def y_path_rect_list_dev(src, in_pitch, w, h, dw, dh, filt, items, stream=None, 
     check(lib().srcnn_y_path_rect_list_f32_dev(_addr(src), int(in_pitch or 0), int(w), int(h), int(dw), int(dh), int(filt),
                                                C.cast(arr, C.c_void_p) if arr is not None else None, count if n is None else int(n),
                                                C.sizeof(RectItem) if item_size is None else int(item_size), handle))
+
+
+def y_path_delta_grid(w, h, dw, dh, filt, tile=(0, 0)):
+    """(cols, rows) of the delta call's tile grid (srcnn_y_path_delta_grid; no device).  tile: (tile_w, tile_h), 0 = the default 64."""
+    cols, rows = C.c_uint(0), C.c_uint(0)
+    check(lib().srcnn_y_path_delta_grid(int(w), int(h), int(dw), int(dh), int(filt), int(tile[0]), int(tile[1]), C.byref(cols), C.byref(rows)))
+    return cols.value, rows.value
+
+
+def y_path_delta_flags_dev(prev, prev_pitch, cur, cur_pitch, w, h, dw, dh, filt, tile, flags, stream=None):
+    """srcnn_y_path_delta_flags_dev on device memory, as given: prev (None = no previous frame) / cur are whole source planes and
+    flags receives cols x rows bytes (see _addr), pitches in bytes (0 = tight).  Asynchronous on `stream`."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_y_path_delta_flags_dev(_addr(prev), int(prev_pitch or 0), _addr(cur), int(cur_pitch or 0), int(w), int(h), int(dw), int(dh),
+                                             int(filt), int(tile[0]), int(tile[1]), _addr(flags), handle))
+
+
+def y_path_delta_rects(flags, tile, dw, dh, out=None, out_pitch=0, cap=None):
+    """srcnn_y_path_delta_rects (pure host): the coalescer over a (rows, cols) uint8 array of flags of tile[0] x tile[1] tiles.
+    Returns [(x0, y0, rw, rh, d_out, out_pitch)].  cap: None = as many items as needed; 0 = count only (returns the number);
+    anything else is the capacity handed to the call (tests)."""
+    flags = np.ascontiguousarray(flags, np.uint8)
+    rows, cols = flags.shape
+    n = C.c_uint(0)
+    args = (flags.ctypes.data, cols, rows, int(tile[0]), int(tile[1]), int(dw), int(dh), _addr(out), int(out_pitch or 0))
+    if cap is None or cap == 0:
+        check(lib().srcnn_y_path_delta_rects(*args, None, 0, C.byref(n)))
+        if cap == 0:
+            return n.value
+        cap = n.value
+    arr = (RectItem * max(1, int(cap)))()
+    check(lib().srcnn_y_path_delta_rects(*args, C.cast(arr, C.c_void_p), int(cap), C.byref(n)))
+    return [(arr[k].x0, arr[k].y0, arr[k].rw, arr[k].rh, arr[k].d_out, arr[k].out_pitch) for k in range(n.value)]
+
+
+def y_path_delta_dev(prev, prev_pitch, cur, cur_pitch, w, h, dw, dh, filt, tile, out, out_pitch, stream=None, stats=True, struct_size=None):
+    """srcnn_y_path_delta_f32_dev on device memory, as given: repaints inside the full-size plane `out` what can differ between
+    prev (None = no previous frame) and cur.  Blocks until the flags have arrived; the upscale is asynchronous on `stream`.
+    Returns the DeltaStats (None with stats=False)."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    st = None
+    if stats:
+        st = DeltaStats()
+        st.struct_size = C.sizeof(DeltaStats) if struct_size is None else int(struct_size)
+    check(lib().srcnn_y_path_delta_f32_dev(_addr(prev), int(prev_pitch or 0), _addr(cur), int(cur_pitch or 0), int(w), int(h), int(dw), int(dh),
+                                           int(filt), int(tile[0]), int(tile[1]), _addr(out), int(out_pitch or 0), handle,
+                                           C.byref(st) if st is not None else None))
+    return st
+
+
+def y_path_delta(prev, cur, out, dw, dh, filt=SRCNNF_Bicubic, tile=(0, 0)):
+    """numpy convenience over srcnn_y_path_delta_f32_dev: `out` (dh x dw float32, the Y path of `prev`; prev None = anything) is
+    updated to the Y path of `cur`.  Returns (out, stats) -- a new array; what the call did not repaint is copied from `out`."""
+    y = _plane(cur)
+    h, w = y.shape
+    o = np.ascontiguousarray(out, np.float32)
+    assert o.shape == (dh, dw), o.shape
+    dprev = DeviceBuffer.from_numpy(_plane(prev)) if prev is not None else None
+    assert prev is None or _plane(prev).shape == y.shape
+    dcur = DeviceBuffer.from_numpy(y)
+    dout = DeviceBuffer.from_numpy(o)
+    st = y_path_delta_dev(dprev, 0, dcur, 0, w, h, dw, dh, filt, tile, dout, 0)
+    sync()
+    return dout.to_numpy(np.float32, (dh, dw)), st
 
 
 def y_path_rects(plane, dw, dh, filt, rects):

@@ -96,7 +96,21 @@ struct Scratch {            // the buffers of a Workspace: movable, so that a wo
     DevBuf<float> win;      // rect call: the layer-3 result of a window (band), tight, before its interior is stored
     DevBuf<unsigned char> bytes;
     DevBuf<unsigned char> list;   // rect list call: the descriptor tables of a call's atlases (written in stream order)
-    size_t footprint() const { return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size() + win.size()) + bytes.size() + list.size(); }
+    DevBuf<unsigned> delta_spans;        // delta call: the span tables of the grid DeltaStage::key names
+    DevBuf<unsigned char> delta_flags;   // delta call: the tile flags of srcnn_y_path_delta_f32_dev
+    size_t footprint() const
+    {
+        return sizeof(float) * (tmp.size() + up.size() + c2.size() + planes.size() + win.size()) + bytes.size() + list.size() +
+               sizeof(unsigned) * delta_spans.size() + delta_flags.size();
+    }
+};
+// What the delta call keeps beside Scratch::delta_spans / delta_flags.  The span tables depend on the geometry alone, so they
+// are uploaded when `key` changes and not again (a stream of frames: once).  `pin` receives the flags of
+// srcnn_y_path_delta_f32_dev, which waits for them before it returns, under the workspace's mutex: one buffer is enough.
+struct DeltaStage {
+    PinnedBuf pin;
+    bool valid = false;
+    unsigned key[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // w, h, dw, dh, filter, tile_w, tile_h, 0
 };
 // Page-locked staging of the rect list call's descriptor tables.  A call fills the next slot of the ring on the host, queues the
 // copy to Scratch::list on its stream and records the slot's event behind it; a slot is written again only after that event has
@@ -114,13 +128,14 @@ struct Workspace : Scratch {          // scratch of one stream / graph / lane; g
     bool queue_dirty = false;                    // a call failed after launching: zero the counters before the next launch
     bool frozen = false;    // a captured graph has these pointers baked in: growing is an error
     ListStaging list_stage;
+    DeltaStage delta_stage;
     template <class T>
     int grow(DevBuf<T>& b, size_t want)          // b: one of this workspace's buffers
     {
         if (want > b.size() && frozen) return fail(SRCNN_E_ARG, "workspace of a captured graph cannot grow (%zu > %zu elements)", want, b.size());
         return b.grow(want);
     }
-    void clear() { static_cast<Scratch&>(*this) = {}; list_stage = {}; (void)hipFree(queue); queue = nullptr; }
+    void clear() { static_cast<Scratch&>(*this) = {}; list_stage = {}; delta_stage = {}; (void)hipFree(queue); queue = nullptr; }
     ~Workspace() { (void)hipFree(queue); }
 };
 

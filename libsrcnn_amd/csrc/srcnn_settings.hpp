@@ -50,7 +50,8 @@
     X(I, rect_list_single_samples, "SRCNN_RECT_LIST_SINGLE_SAMPLES", 2097152, "samples of a cell, (rw + 12) x (rh + 12)", "rect list call: items whose cell has at least this many samples run as single rect calls.  Started at 524288 (512 tiles of 64x16, one round of the persistent layer-1+2 grid); the sweep of `profiles/rect_list_probe.txt` found no crossover there -- 16 rects of 768x768 and 1024x1024 were still 1.4x and 1.3x faster batched than looped -- so it stands at 2^21, the largest cell that sweep measures.  The RGB(A) and the YUV rect list calls route by the same threshold") \
     X(B, rgb_rect_list_unfused, "SRCNN_RGB_RECT_LIST_UNFUSED", 0, "0/1", "RGB(A) rect list call: every item as a single RGB(A) rect call instead of small rects sharing one atlas per layer launch, with Y read and colour merged by `k_rgb_list_resample` / `k_rgb_list_merge`") \
     X(B, yuv_rect_list_unfused, "SRCNN_YUV_RECT_LIST_UNFUSED", 0, "0/1", "planar / semi-planar YUV rect list call: every item as a single YUV rect call instead of small rects sharing one atlas per layer launch, with luma read and written by `k_yuv_list_resample` / `k_yuv_list_luma` and chroma by `k_yuv_list_chroma`") \
-    X(B, yuv_packed_rect_list_unfused, "SRCNN_YUV_PACKED_RECT_LIST_UNFUSED", 0, "0/1", "packed YUV rect list call: every item as a single packed YUV rect call instead of small rects sharing one atlas per layer launch, with luma read by `k_yuvp_list_resample` and chroma / alpha resampled, merged with Y' and stored by `k_yuvp_list_merge`")
+    X(B, yuv_packed_rect_list_unfused, "SRCNN_YUV_PACKED_RECT_LIST_UNFUSED", 0, "0/1", "packed YUV rect list call: every item as a single packed YUV rect call instead of small rects sharing one atlas per layer launch, with luma read by `k_yuvp_list_resample` and chroma / alpha resampled, merged with Y' and stored by `k_yuvp_list_merge`") \
+    X(I, delta_whole_permille, "SRCNN_DELTA_WHOLE_PERMILLE", 850, "permille of `dw * dh`", "delta call (`srcnn_y_path_delta_f32_dev`): the frame is repainted as one rect instead of the coalesced dirty rects when the sum of their cells, (rw + 12) x (rh + 12), reaches this share of the output frame.  Started at 1000, where the list certainly does more layer work than the frame; `profiles/delta_probe.txt` measures the crossover on a 3840x2160 -> 7680x4320 frame: at 0.867 (one block of 85 % of the tiles) the list route still beats the whole frame by 10 %, at 0.877 (a random 70 % of the tiles, 1693 rects) it is 1.5 % behind -- rounded down to 50, never below 500.  Either route gives the same bits")
 
 namespace srcnn {
 
