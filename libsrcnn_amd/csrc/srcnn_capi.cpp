@@ -432,6 +432,7 @@ int get_table(Call& c, int filter, unsigned dst_len, unsigned src_len, TableRef&
         auto d = std::make_shared<DeviceTable>();
         d->stride = t.stride;
         d->max_taps = t.max_taps;
+        d->src_len = src_len;
         d->h_first.assign(t.first.begin(), t.first.end());
         d->h_taps.assign(t.taps.begin(), t.taps.end());
         d->monotone = true;
@@ -832,7 +833,6 @@ int resample_src_rows(Call& c, const YSource& src, unsigned sw, unsigned sh, uns
                 if ((rc = get_table(c, filter, dh, sh, tv))) return rc;
                 unsigned lo = 0, hi = sh;
                 tv->source_span(r0, r1, lo, hi);
-                hi = std::min(hi, sh);
                 if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for rows [%u,%u)", r0, r1);
                 if ((rc = ws.grow(ws.tmp, (size_t)dw * (hi - lo)))) return rc;
                 launch_resample_rows(d_in + (size_t)lo * sw, sw, ws.tmp.data(), dw, hi - lo, view_of(th), s);
@@ -894,7 +894,6 @@ int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0
         // horizontal first, over the source rows the vertical taps of rows [r0, r1) read, then vertical
         unsigned lo = 0, hi = sh;
         tv->source_span(r0, r1, lo, hi);
-        hi = std::min(hi, sh);
         if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for rows [%u,%u)", r0, r1);
         if ((rc = ws.grow(ws.tmp, (size_t)nc * (hi - lo)))) return rc;
         launch_window_rows(d_in + (size_t)(lo - in_y0) * in_stride, in_stride, (int)in_x0, ws.tmp.data(), (int)c0, nc, (int)(hi - lo), view_of(th), s);
@@ -903,7 +902,6 @@ int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0
         // vertical first, over the source columns the horizontal taps of columns [c0, c1) read, then horizontal
         unsigned lo = 0, hi = sw;
         th->source_span(c0, c1, lo, hi);
-        hi = std::min(hi, sw);
         if (hi <= lo) return fail(SRCNN_E_UNSUPPORTED, "empty source span for columns [%u,%u)", c0, c1);
         if ((rc = ws.grow(ws.tmp, (size_t)(hi - lo) * nr))) return rc;
         launch_window_cols(d_in + (lo - in_x0), in_stride, (int)in_y0, ws.tmp.data(), (int)(hi - lo), (int)r0, nr, view_of(tv), s);
@@ -925,59 +923,77 @@ int check_plane(const void* in, unsigned w, unsigned h, const void* out)
     return SRCNN_OK;
 }
 
-// resample + conv12 + conv3 for output rows [r0,r1) of the (dw x dh) result.
-int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
-                unsigned r0, unsigned r1, float* d_out)
+namespace {
+
+static_assert(kLayer2Planes == (unsigned)C2N, "srcnn_y_path_geom.hpp sizes the layer-2 scratch");
+
+// The one pass of the Y path: resample + conv12 + conv3 for output rows [r0,r1) of a window of the upscaled plane that is W
+// floats wide and dh rows high (the whole plane, or a rect's columns with their halo), into d_out (W floats per row, row r0
+// first).  resample(ua, ub) fills ws.up with rows [ua,ub) of that window; store() launches what the route still owes its caller,
+// outside the stage timers and before the error check; `who` names the route in the error text, label... is the printf-style
+// trace label of the strict sequence (the fused tier opens none).  Every buffer is grown before the first launch: growing drains
+// the device.
+// (list_batched of srcnn_rect_list_call.hpp runs the same three stages with launch_list_replicate between them: it stays apart)
+template <class Resample, class Store, class... Label>
+int y_path_pass(Call& c, const char* who, unsigned W, unsigned dh, unsigned r0, unsigned r1, float* d_out, Resample resample, Store store,
+                Label... label)
 {
-    if (r1 > dh || r0 >= r1) return fail(SRCNN_E_ARG, "row range [%u,%u) outside 0..%u", r0, r1, dh);
-    if (dh > (1u << 20) || h > (1u << 20) || dw > 0x7fffffu || (r1 - r0) > 65535u * 16u)
-        return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
     Workspace& ws = *c.ws;
-    [[maybe_unused]] Ctx& cx = *c.cx;
-    // rows of layer-2 activations that conv3 touches (clamp-to-edge of the ACTIVATIONS at the true
-    // border), and rows of upscaled Y that conv1 touches for those.
-    const unsigned ca = r0 >= 2 ? r0 - 2 : 0, cb = std::min(dh, r1 + 2);
-    const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dh, cb + 4);
+    const HaloSpan v = y_path_halo(dh, r0, r1);
     int rc;
-    if ((rc = ws.grow(ws.up, (size_t)dw * (ub - ua)))) return rc;
+    if ((rc = ws.grow(ws.up, (size_t)W * (v.ub - v.ua)))) return rc;
 #ifndef SRCNN_STRICT_ONLY
-    const bool fused = c.mode == SRCNN_MODE_FAST_F16;
-    if (fused) {
+    if (c.mode == SRCNN_MODE_FAST_F16) {
         // non-parity tier: one kernel for all three layers, no layer-2 planes at all
         {
             StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-            if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up.data()))) return rc;
+            if ((rc = resample(v.ua, v.ub))) return rc;
         }
         {
             StageTimer t(SRCNN_STAGE_CONV12, c);
-            launch_fused_f16(ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), d_out, (int)r0, (int)(r1 - r0), cx.fused_w.data(),
-                             cx.num_cus, c.s);
+            launch_fused_f16(ws.up.data(), (int)W, (int)dh, (int)v.ua, (int)(v.ub - v.ua), d_out, (int)r0, (int)(r1 - r0), c.cx->fused_w.data(),
+                             c.cx->num_cus, c.s);
         }
+        store();
         HIP_TRY(hipGetLastError());
         return SRCNN_OK;
     }
 #endif
-    if ((rc = ws.grow(ws.c2, (size_t)C2N * dw * (cb - ca)))) return rc;
-    TraceRange tr("srcnn y_path rows [%u,%u) of %ux%u", r0, r1, dw, dh);
+    const size_t plane = (size_t)W * (v.cb - v.ca);
+    if ((rc = ws.grow(ws.c2, (size_t)C2N * plane))) return rc;
+    TraceRange tr(label...);
     {
         StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-        if ((rc = resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, ws.up.data()))) return rc;
+        if ((rc = resample(v.ua, v.ub))) return rc;
     }
-    const size_t plane = (size_t)dw * (cb - ca);
     {
         StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_conv12(c, ws.up.data(), (int)dw, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
+        run_conv12(c, ws.up.data(), (int)W, (int)dh, (int)v.ua, (int)(v.ub - v.ua), ws.c2.data(), plane, (int)v.ca, (int)(v.cb - v.ca));
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_layer3(ws.c2.data(), plane, (int)dw, (int)dh, (int)ca, (int)(cb - ca), d_out, (int)r0, (int)(r1 - r0),
-                     c.relax(), c.s);
+        launch_layer3(ws.c2.data(), plane, (int)W, (int)dh, (int)v.ca, (int)(v.cb - v.ca), d_out, (int)r0, (int)(r1 - r0), c.relax(), c.s);
     }
+    store();
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
         ws.queue_dirty = true;                         // re-zeroed on the launch stream before the next launch trusts it
-        return fail(SRCNN_E_HIP, "y_path_rows: %s", hipGetErrorString(e));
+        return fail(SRCNN_E_HIP, "%s: %s", who, hipGetErrorString(e));
     }
     return SRCNN_OK;
+}
+
+}  // namespace
+
+// The pass over whole rows: output rows [r0,r1) of the (dw x dh) result.
+int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
+                unsigned r0, unsigned r1, float* d_out)
+{
+    if (r1 > dh || r0 >= r1) return fail(SRCNN_E_ARG, "row range [%u,%u) outside 0..%u", r0, r1, dh);
+    if (!y_path_fits(0, h, dw, dh, r1 - r0)) return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
+    return y_path_pass(
+        c, "y_path_rows", dw, dh, r0, r1, d_out,
+        [&](unsigned ua, unsigned ub) { return resample_src_rows(c, src, w, h, dw, dh, filter, ua, ub, c.ws->up.data()); }, [] {},
+        "srcnn y_path rows [%u,%u) of %ux%u", r0, r1, dw, dh);
 }
 
 // Source rows [lo,hi) of the (w x h) input that output rows [r0,r1) of the Y path depend on: +-2 rows of layer-2
@@ -985,24 +1001,21 @@ int y_path_rows(Call& c, const YSource& src, unsigned w, unsigned h, unsigned dw
 // contribution table itself, so it is exact for every filter and ratio.
 int y_path_source_rows(Call& c, unsigned h, unsigned dh, int filter, unsigned r0, unsigned r1, unsigned& lo, unsigned& hi)
 {
-    const unsigned ca = r0 >= 2 ? r0 - 2 : 0, cb = std::min(dh, r1 + 2);
-    const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dh, cb + 4);
-    if (h == dh) { lo = ua; hi = ub; return SRCNN_OK; }
+    const HaloSpan v = y_path_halo(dh, r0, r1);
+    if (h == dh) { lo = v.ua; hi = v.ub; return SRCNN_OK; }
     TableRef tv;
     int rc = get_table(c, filter, dh, h, tv);
     if (rc) return rc;
-    tv->source_span(ua, ub, lo, hi);
-    hi = std::min(hi, h);
+    tv->source_span(v.ua, v.ub, lo, hi);
     return SRCNN_OK;
 }
 
-unsigned budget_band_rows(unsigned dw)
+// (1 << 20 rows: the most a band ever has, and what the function returns when even they fit)
+unsigned budget_band_rows(unsigned dw) { return y_path_band_rows(G.ws_budget.load(), false, dw, 1u << 20); }
+
+unsigned y_path_pass_rows(const Call& c, unsigned W, unsigned rows)
 {
-    const size_t budget = G.ws_budget.load();
-    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
-    const size_t fit = budget / row_bytes;
-    // 16-row floor: one tile row of the layer kernels (a smaller limit is exceeded rather than refused; srcnn_amd.h says so)
-    return (unsigned)std::min<size_t>(std::max<size_t>(16, fit > 4 ? fit - 4 : 1), 1u << 20);
+    return y_path_band_rows(G.ws_budget.load(), c.mode == SRCNN_MODE_FAST_F16, W, rows);
 }
 
 // Cut output rows [R0,R1) of a (dw x dh) frame into pieces of about frac[0], frac[1], ... of the range (the last piece takes the
@@ -1051,13 +1064,9 @@ std::vector<unsigned> plan_cuts(unsigned R0, unsigned R1, unsigned dw, unsigned 
 int y_path_range(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter,
                  unsigned r0, unsigned r1, float* d_out)
 {
-    const size_t budget = G.ws_budget.load();
     if (r1 > dh || r0 >= r1) return fail(SRCNN_E_ARG, "row range [%u,%u) outside 0..%u", r0, r1, dh);
-    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
-    const bool no_planes = c.mode == SRCNN_MODE_FAST_F16;      // the fused kernel has no layer-2 planes
     const YSource src = YSource::from_plane(d_in);
-    if (no_planes || row_bytes * ((size_t)(r1 - r0) + 4) <= budget) return y_path_rows(c, src, w, h, dw, dh, filter, r0, r1, d_out);
-    const unsigned band = budget_band_rows(dw);
+    const unsigned band = y_path_pass_rows(c, dw, r1 - r0);      // (all of them: one pass)
     for (unsigned a = r0; a < r1; a += band) {
         const unsigned b = std::min(r1, a + band);
         int rc = y_path_rows(c, src, w, h, dw, dh, filter, a, b, d_out + (size_t)(a - r0) * dw);
@@ -1074,63 +1083,24 @@ int y_path_frame(Call& c, const float* d_in, unsigned w, unsigned h, unsigned dw
 namespace {
 
 // Output samples [x0,x1) x [r0,r1) in one pass.  A pixel's arithmetic does not depend on where its tile lies, so a window of
-// the upscaled plane goes through the unchanged layer kernels as if it were a Ww-wide frame of dh rows: columns [uax,ubx) =
-// the rect + 2 (layer 3) + 4 (layer 1), cut short at the true borders.  The kernels' clamp-to-edge is then wrong only inside
-// that halo, which the store leaves behind; where the window ends at a true border the clamp is the frame's own.  Rows are
-// handled as y_path_rows handles them (H and the row bases are the true ones).  (in_x0, in_y0): the sample of the w x h plane
-// at which d_in begins.
+// the upscaled plane goes through the unchanged layer kernels as if it were a Ww-wide frame of dh rows: the columns of
+// y_path_halo(dw, x0, x1), the rect + 2 (layer 3) + 4 (layer 1), cut short at the true borders.  The kernels' clamp-to-edge is
+// then wrong only inside that halo, which the store leaves behind; where the window ends at a true border the clamp is the
+// frame's own.  Rows are the pass's, as for y_path_rows (H and the row bases are the true ones).  (in_x0, in_y0): the sample of
+// the w x h plane at which d_in begins.
 int y_path_rect_rows(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned w, unsigned h,
                      unsigned dw, unsigned dh, int filter, unsigned x0, unsigned x1, unsigned r0, unsigned r1, float* d_out,
                      size_t out_stride)
 {
     Workspace& ws = *c.ws;
-    [[maybe_unused]] Ctx& cx = *c.cx;
-    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
-    const unsigned uax = cax >= 4 ? cax - 4 : 0, ubx = std::min(dw, cbx + 4);
-    const unsigned Ww = ubx - uax;
-    const unsigned ca = r0 >= 2 ? r0 - 2 : 0, cb = std::min(dh, r1 + 2);
-    const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dh, cb + 4);
-    int rc;
-    if ((rc = ws.grow(ws.up, (size_t)Ww * (ub - ua)))) return rc;
-    if ((rc = ws.grow(ws.win, (size_t)Ww * (r1 - r0)))) return rc;
-    const float* interior = ws.win.data() + (x0 - uax);
-#ifndef SRCNN_STRICT_ONLY
-    if (c.mode == SRCNN_MODE_FAST_F16) {
-        {
-            StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-            if ((rc = resample_window(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
-        }
-        {
-            StageTimer t(SRCNN_STAGE_CONV12, c);
-            launch_fused_f16(ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.win.data(), (int)r0, (int)(r1 - r0), cx.fused_w.data(),
-                             cx.num_cus, c.s);
-        }
-        launch_window_copy(interior, Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s);
-        HIP_TRY(hipGetLastError());
-        return SRCNN_OK;
-    }
-#endif
-    if ((rc = ws.grow(ws.c2, (size_t)C2N * Ww * (cb - ca)))) return rc;
-    TraceRange tr("srcnn y_path rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, r0, r1, dw, dh);
-    {
-        StageTimer t(SRCNN_STAGE_RESAMPLE, c);
-        if ((rc = resample_window(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, uax, ubx, ua, ub, ws.up.data()))) return rc;
-    }
-    const size_t plane = (size_t)Ww * (cb - ca);
-    {
-        StageTimer t(SRCNN_STAGE_CONV12, c);
-        run_conv12(c, ws.up.data(), (int)Ww, (int)dh, (int)ua, (int)(ub - ua), ws.c2.data(), plane, (int)ca, (int)(cb - ca));
-    }
-    {
-        StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_layer3(ws.c2.data(), plane, (int)Ww, (int)dh, (int)ca, (int)(cb - ca), ws.win.data(), (int)r0, (int)(r1 - r0), c.relax(), c.s);
-    }
-    launch_window_copy(interior, Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s);      // (outside the stage timers)
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-        ws.queue_dirty = true;
-        return fail(SRCNN_E_HIP, "y_path_rect: %s", hipGetErrorString(e));
-    }
-    return SRCNN_OK;
+    const HaloSpan hx = y_path_halo(dw, x0, x1);
+    const unsigned Ww = hx.width();
+    if (int rc = ws.grow(ws.win, (size_t)Ww * (r1 - r0))) return rc;
+    return y_path_pass(
+        c, "y_path_rect", Ww, dh, r0, r1, ws.win.data(),
+        [&](unsigned ua, unsigned ub) { return resample_window(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, hx.ua, hx.ub, ua, ub, ws.up.data()); },
+        [&] { launch_window_copy(ws.win.data() + (x0 - hx.ua), Ww, d_out, out_stride, (int)(x1 - x0), (int)(r1 - r0), c.s); },
+        "srcnn y_path rect [%u,%u)x[%u,%u) of %ux%u", x0, x1, r0, r1, dw, dh);
 }
 
 }  // namespace
@@ -1143,33 +1113,16 @@ int y_path_rect(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, un
                 unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1, unsigned y1, float* d_out, size_t out_stride, bool whole_plane)
 {
     if (x1 > dw || x0 >= x1 || y1 > dh || y0 >= y1) return fail(SRCNN_E_ARG, "rect [%u,%u)x[%u,%u) outside %ux%u", x0, x1, y0, y1, dw, dh);
-    if (dh > (1u << 20) || h > (1u << 20) || dw > 0x7fffffu || (y1 - y0) > 65535u * 16u)
-        return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
+    if (!y_path_fits(0, h, dw, dh, y1 - y0)) return fail(SRCNN_E_UNSUPPORTED, "output %ux%u too large", dw, dh);
     if (x0 == 0 && x1 == dw && whole_plane && in_x0 == 0 && in_y0 == 0 && in_stride == w && out_stride == dw)
         return y_path_range(c, d_in, w, h, dw, dh, filter, y0, y1, d_out);
-    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
-    const unsigned Ww = std::min(dw, cbx + 4) - (cax >= 4 ? cax - 4 : 0);
-    const size_t row_bytes = (size_t)C2N * Ww * sizeof(float);
-    const bool no_planes = c.mode == SRCNN_MODE_FAST_F16;      // the fused kernel has no layer-2 planes
-    if (no_planes || row_bytes * ((size_t)(y1 - y0) + 4) <= G.ws_budget.load())
-        return y_path_rect_rows(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, x0, x1, y0, y1, d_out, out_stride);
-    const unsigned band = budget_band_rows(Ww);
+    const unsigned band = y_path_pass_rows(c, y_path_halo(dw, x0, x1).width(), y1 - y0);
     for (unsigned a = y0; a < y1; a += band) {
         const unsigned b = std::min(y1, a + band);
         int rc = y_path_rect_rows(c, d_in, in_stride, in_x0, in_y0, w, h, dw, dh, filter, x0, x1, a, b, d_out + (size_t)(a - y0) * out_stride, out_stride);
         if (rc) return rc;
     }
     return SRCNN_OK;
-}
-
-// Rows of the rect [x0,x1) x [y0,y1) that one pass of y_path_rect produces: all of them, or the band its loop above takes.
-unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1)
-{
-    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
-    const unsigned Ww = std::min(dw, cbx + 4) - (cax >= 4 ? cax - 4 : 0);
-    const size_t row_bytes = (size_t)C2N * Ww * sizeof(float);
-    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)(y1 - y0) + 4) <= G.ws_budget.load()) return y1 - y0;
-    return std::min(y1 - y0, budget_band_rows(Ww));
 }
 
 int check_y_path_args(const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const float* d_out)
@@ -1599,8 +1552,7 @@ int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int fi
 
 int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned rh)
 {
-    if (h > (1u << 20) || dh > (1u << 20) || dw > 0x7fffffu || rh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL)
-        return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
+    if (!y_path_fits((unsigned long long)w * h, h, dw, dh, rh)) return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
     return SRCNN_OK;
 }
 
@@ -1774,7 +1726,7 @@ int srcnn_conv3_f32_dev(const float* d_c2, unsigned w, unsigned h, float* d_out,
 {
     int rc;
     if ((rc = check_plane(d_c2, w, h, d_out))) return rc;
-    if (h > 65535u * 16u) return fail(SRCNN_E_UNSUPPORTED, "too many rows");
+    if (h > kMaxGridRows) return fail(SRCNN_E_UNSUPPORTED, "too many rows");
     if (!ctx_for_stream(stream)) return SRCNN_E_NODEVICE;
     Call c;
     c.mode = G.mode.load();

@@ -41,8 +41,8 @@ inline int delta_grid(unsigned w, unsigned h, unsigned dw, unsigned dh, int filt
     g.tile_h = tile_h ? tile_h : kDeltaTileDefault;
     if (g.tile_w < kDeltaTileMin || g.tile_w > kDeltaTileMax || g.tile_h < kDeltaTileMin || g.tile_h > kDeltaTileMax)
         return fail(SRCNN_E_ARG, "tile %ux%u: a side is 0 (the default, %u) or %u ... %u", tile_w, tile_h, kDeltaTileDefault, kDeltaTileMin, kDeltaTileMax);
-    // the Y path's limits for the frame as one rect (check_rect_limits of srcnn_capi.cpp with rh = dh)
-    if (h > (1u << 20) || dh > 65535u * 16u || dw > 0x7fffffu || (unsigned long long)w * h > 0x7fffffffULL)
+    // the Y path's limits for the frame as one rect
+    if (!y_path_fits((unsigned long long)w * h, h, dw, dh, dh))
         return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
     g.cols = (dw + g.tile_w - 1) / g.tile_w;
     g.rows = (dh + g.tile_h - 1) / g.tile_h;
@@ -61,12 +61,9 @@ inline void delta_axis_spans(const int* first, const int* taps, unsigned dst_len
     out.resize(n);
     for (unsigned k = 0; k < n; ++k) {
         const unsigned a = k * tile, b = std::min(dst_len, a + tile);
-        const unsigned ca = a >= 2 ? a - 2 : 0, cb = std::min(dst_len, b + 2);
-        const unsigned ua = ca >= 4 ? ca - 4 : 0, ub = std::min(dst_len, cb + 4);
-        if (dst_len == src_len) { out[k] = DeltaSpan{ua, ub}; continue; }
-        int l = 0x7fffffff, e = 0;
-        for (unsigned u = ua; u < ub; ++u) { l = std::min(l, first[u]); e = std::max(e, first[u] + taps[u]); }
-        out[k] = DeltaSpan{(unsigned)l, std::min((unsigned)e, src_len)};
+        const HaloSpan v = y_path_halo(dst_len, a, b);
+        if (dst_len == src_len) out[k] = DeltaSpan{v.ua, v.ub};
+        else taps_span(first, taps, src_len, v.ua, v.ub, out[k].lo, out[k].hi);
     }
 }
 

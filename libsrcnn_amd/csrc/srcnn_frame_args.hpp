@@ -12,6 +12,7 @@
 #include "../../include/srcnn_amd_yuv_ex.h"
 #include "../../include/srcnn_amd_yuv_packed.h"
 #include "srcnn_frame_rules.h"
+#include "srcnn_y_path_geom.hpp"
 
 namespace srcnn {
 
@@ -133,7 +134,7 @@ inline int check_scale(unsigned w, unsigned h, float multiply, int filter, unsig
     if ((float)w * multiply >= 8388608.f || (float)h * multiply >= 1048577.f)
         return fail(SRCNN_E_UNSUPPORTED, "output of %ux%u x %g too large", w, h, multiply);
     if (srcnn_output_size(w, h, multiply, 0, &dw, &dh) != SRCNN_OK) return fail(SRCNN_E_SCALE, "scaled size of %ux%u x %g is zero", w, h, multiply);
-    if (h > (1u << 20) || dh > 65535u * 16u || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
+    if (h > (1u << 20) || dh > kMaxGridRows || (unsigned long long)w * h > 0x7fffffffULL || (unsigned long long)dw * dh > 0x7fffffffULL)
         return fail(SRCNN_E_UNSUPPORTED, "%ux%u -> %ux%u is beyond the Y path's limits", w, h, dw, dh);
     return SRCNN_OK;
 }

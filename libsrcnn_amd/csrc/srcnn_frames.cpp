@@ -38,15 +38,6 @@ struct PlaneArena {
     size_t take(size_t k) { const size_t o = (n + 63) & ~(size_t)63; n = o + k; return o; }
 };
 
-// Rows of Y' one pass of the Y path produces: the whole frame when its layer-2 planes fit the workspace cap (y_path_range's
-// test), else budget_band_rows.
-unsigned yuv_band_rows(const Call& c, unsigned dw, unsigned dh)
-{
-    const size_t row_bytes = (size_t)C2N * dw * sizeof(float);
-    if (c.mode == SRCNN_MODE_FAST_F16 || row_bytes * ((size_t)dh + 4) <= G.ws_budget.load()) return dh;
-    return std::min(dh, budget_band_rows(dw));
-}
-
 // Y' in bands of `band` rows: the Y path writes rows [a, b) to yband, then after(a, b) packs them into the destination.
 template <class After>
 int for_each_y_band(Call& c, const YSource& ysrc, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned band,
@@ -68,7 +59,7 @@ int yuv_frame(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, un
 {
     Workspace& ws = *c.ws;
     const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
-    const unsigned band = yuv_band_rows(c, dw, dh);
+    const unsigned band = y_path_pass_rows(c, dw, dh);
     PlaneArena A;
     const size_t o_y = A.take((size_t)w * h), o_u = A.take((size_t)cw * ch), o_v = A.take((size_t)cw * ch);
     const size_t o_cu = A.take((size_t)dcw * dch), o_cv = A.take((size_t)dcw * dch), o_band = A.take((size_t)dw * band);
@@ -109,7 +100,7 @@ int yuv_packed_frame(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, un
 {
     Workspace& ws = *c.ws;
     const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
-    const unsigned band = yuv_band_rows(c, dw, dh);
+    const unsigned band = y_path_pass_rows(c, dw, dh);
     // [Y U V (A) at source size] [U' V' (A') at output size] [Y' of one band]
     PlaneArena A;
     const size_t o_y = A.take((size_t)w * h), o_u = A.take((size_t)cw * h), o_v = A.take((size_t)cw * h);
@@ -155,7 +146,7 @@ int rgb_frame(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, un
 {
     Workspace& ws = *c.ws;
     const int cfilter = chroma_filter(filter);
-    const unsigned band = yuv_band_rows(c, dw, dh);
+    const unsigned band = y_path_pass_rows(c, dw, dh);
     int rc;
     const bool tight = in[0].pitch == in[0].row_bytes && out[0].pitch == out[0].row_bytes && (!conv.lo || conv.pitch == conv.row_bytes);
     // (as in process_share: the switches that force the plane resamplers select the plane shell as well)
@@ -210,16 +201,7 @@ int axis_span(Call& c, int filter, unsigned dst_len, unsigned src_len, unsigned 
     int rc;
     if ((rc = get_table(c, filter, dst_len, src_len, t))) return rc;
     t->source_span(a, b, lo, hi);
-    hi = std::min(hi, src_len);
     return SRCNN_OK;
-}
-
-// [lo, hi) of an output axis the Y path computes for the rect's [a, b): +-2 (layer 3), +-4 (layer 1), cut at the borders
-void halo_span(unsigned len, unsigned a, unsigned b, unsigned& lo, unsigned& hi)
-{
-    const unsigned ca = a >= 2 ? a - 2 : 0, cb = std::min(len, b + 2);
-    lo = ca >= 4 ? ca - 4 : 0;
-    hi = std::min(len, cb + 4);
 }
 
 // The source rectangles of a rect, each [lx, hx) x [ly, hy): what the Y path reads of the luma plane (the halo of the luma rect,
@@ -237,11 +219,9 @@ int rect_source(Call& c, int filter, int cfilter, unsigned w, unsigned h, unsign
                 RectSource& r)
 {
     int rc;
-    unsigned ha, hb;
-    halo_span(dw, x0, x1, ha, hb);
-    if ((rc = axis_span(c, filter, dw, w, ha, hb, r.ylx, r.yhx))) return rc;
-    halo_span(dh, y0, y1, ha, hb);
-    if ((rc = axis_span(c, filter, dh, h, ha, hb, r.yly, r.yhy))) return rc;
+    const HaloSpan vx = y_path_halo(dw, x0, x1), vy = y_path_halo(dh, y0, y1);
+    if ((rc = axis_span(c, filter, dw, w, vx.ua, vx.ub, r.ylx, r.yhx))) return rc;
+    if ((rc = axis_span(c, filter, dh, h, vy.ua, vy.ub, r.yly, r.yhy))) return rc;
     if ((rc = axis_span(c, cfilter, dcw, cw, cx0, cx1, r.clx, r.chx))) return rc;
     if ((rc = axis_span(c, cfilter, dch, ch, cy0, cy1, r.cly, r.chy))) return rc;
     return SRCNN_OK;
@@ -280,7 +260,7 @@ int rgb_rect(Call& c, const RgbRule& g, unsigned w, unsigned h, unsigned dw, uns
     Workspace& ws = *c.ws;
     const int cfilter = chroma_filter(filter);
     const unsigned rw = x1 - x0;
-    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    const unsigned band = y_path_pass_rows(c, y_path_halo(dw, x0, x1).width(), y1 - y0);
     int rc;
     RectSource r;
     if ((rc = rect_source(c, filter, cfilter, w, h, dw, dh, w, h, dw, dh, x0, y0, x1, y1, x0, y0, x1, y1, r))) return rc;
@@ -352,7 +332,7 @@ int yuv_rect(Call& c, const YuvGeom& g, unsigned w, unsigned h, unsigned dw, uns
     const YuvChromaRect cr(g, x0, y0, x1, y1);
     const unsigned rw = x1 - x0, crw = cr.cx1 - cr.cx0, crh = cr.cy1 - cr.cy0;
     const unsigned cw = g.ccols(w), ch = g.crows(h), dcw = g.ccols(dw), dch = g.crows(dh);
-    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    const unsigned band = y_path_pass_rows(c, y_path_halo(dw, x0, x1).width(), y1 - y0);
     const unsigned spp = g.semi ? 2 : 1;                 // samples per column of a chroma plane
     const int ncp = g.semi ? 1 : 2;                      // chroma planes in memory
     int rc;
@@ -423,7 +403,7 @@ int yuv_packed_rect(Call& c, const YuvPackedGeom& g, unsigned w, unsigned h, uns
     const YuvPackedChromaCols cc(kind, x0, x1);
     const unsigned rw = x1 - x0, crw = cc.cx1 - cc.cx0;
     const unsigned cw = g.ccols(w), dcw = g.ccols(dw);
-    const unsigned band = y_path_rect_band_rows(c, dw, x0, x1, y0, y1);
+    const unsigned band = y_path_pass_rows(c, y_path_halo(dw, x0, x1).width(), y1 - y0);
     int rc;
     RectSource r;
     if ((rc = rect_source(c, filter, cfilter, w, h, dw, dh, cw, h, dcw, dh, x0, y0, x1, y1, cc.cx0, y0, cc.cx1, y1, r))) return rc;

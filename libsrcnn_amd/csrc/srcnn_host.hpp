@@ -28,6 +28,7 @@
 #include "srcnn_kernels.h"
 #include "srcnn_owned.hpp"
 #include "srcnn_settings.hpp"
+#include "srcnn_y_path_geom.hpp"
 
 namespace srcnn {
 
@@ -78,13 +79,9 @@ struct DeviceTable {          // one uploaded AxisTable; freed only when the las
     std::vector<int> h_first, h_taps;
     bool monotone = false;             // first[] and first[]+taps[] both non-decreasing: a tile's span is given by its ends
     DevAxisTable view() const { return DevAxisTable{first.data(), taps.data(), weight.data(), stride, max_taps, monotone ? 1 : 0, h_first.data(), h_taps.data()}; }
+    unsigned src_len = 0;              // of the axis the taps read
     // source index range [lo, hi) read by destination indices [a, b)
-    void source_span(unsigned a, unsigned b, unsigned& lo, unsigned& hi) const
-    {
-        int l = 0x7fffffff, h = 0;
-        for (unsigned u = a; u < b; ++u) { l = h_first[u] < l ? h_first[u] : l; const int e = h_first[u] + h_taps[u]; h = e > h ? e : h; }
-        lo = (unsigned)l; hi = (unsigned)h;
-    }
+    void source_span(unsigned a, unsigned b, unsigned& lo, unsigned& hi) const { taps_span(h_first.data(), h_taps.data(), src_len, a, b, lo, hi); }
 };
 using TableRef = std::shared_ptr<DeviceTable>;
 
@@ -374,8 +371,9 @@ int check_rect_geometry(unsigned w, unsigned h, unsigned dw, unsigned dh, int fi
 int check_rect_limits(unsigned w, unsigned h, unsigned dw, unsigned dh, unsigned rh);
 // layers 1+2 over rows of a (W x H) plane, as every path launches them (kernel instance, tile queue of the workspace, clock probe)
 void run_conv12(const Call& c, const float* Y, int W, int H, int y_row_base, int y_rows, float* C2, size_t plane, int row0, int rows);
-// rows of that rect one pass produces: all of them, or the band y_path_rect cuts it into under the workspace budget
-unsigned y_path_rect_band_rows(const Call& c, unsigned dw, unsigned x0, unsigned x1, unsigned y0, unsigned y1);
+// rows of `rows` one pass of the Y path produces over a window W floats wide (y_path_band_rows under the workspace budget): the
+// band y_path_range (W = dw) and y_path_rect (W = the width of the rect's halo) cut their ranges into
+unsigned y_path_pass_rows(const Call& c, unsigned W, unsigned rows);
 // Columns [c0,c1) x rows [r0,r1) of the resampled (dw x dh) plane, tight, at the cost of that window, with the bits of
 // resample_rows_range; d_in (in_stride floats per row) begins at sample (in_x0, in_y0) of the sw x sh source plane.
 int resample_window(Call& c, const float* d_in, size_t in_stride, unsigned in_x0, unsigned in_y0, unsigned sw, unsigned sh,

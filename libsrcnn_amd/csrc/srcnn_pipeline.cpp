@@ -385,7 +385,7 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
             if ((rc = get_table(c, J.cfilter, dh, h, cv))) return rc;
             unsigned clo, chi;
             cv->source_span(R0, R1, clo, chi);
-            lo = std::min(lo, clo); hi = std::max(hi, std::min(chi, h));
+            lo = std::min(lo, clo); hi = std::max(hi, chi);
         } else { lo = std::min(lo, R0); hi = std::max(hi, R1); }
     }
     // The fused shell reads the interleaved source directly (no split, no destination-size chroma planes); it needs an
@@ -500,7 +500,7 @@ int process_share(Ctx& cx, const ProcJob& J, unsigned R0, unsigned R1, bool one_
         unsigned l2 = 0, h2 = hi;
         int r = y_path_source_rows(c, h, dh, J.filter, a, b, l2, h2);
         if (r) return r;
-        if (cv) { unsigned cl, chh; cv->source_span(a, b, cl, chh); h2 = std::max(h2, std::min(chh, h)); }
+        if (cv) { unsigned cl, chh; cv->source_span(a, b, cl, chh); h2 = std::max(h2, chh); }
         else h2 = std::max(h2, std::min(b, h));
         upto = std::min(h2, hi);
         return SRCNN_OK;

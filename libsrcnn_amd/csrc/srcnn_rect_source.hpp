@@ -9,6 +9,7 @@
 #include "resample_table.hpp"
 #include "srcnn_frame_args.hpp"
 #include "srcnn_window_tile.h"
+#include "srcnn_y_path_geom.hpp"
 
 namespace srcnn {
 
@@ -18,10 +19,7 @@ inline void axis_source_span(int filter, unsigned dst_len, unsigned src_len, uns
 {
     if (dst_len == src_len) { lo = a; hi = b; return; }
     const AxisTable t = build_axis_table(filter, dst_len, src_len);
-    int l = 0x7fffffff, e = 0;
-    for (unsigned u = a; u < b; ++u) { l = std::min(l, (int)t.first[u]); e = std::max(e, (int)(t.first[u] + t.taps[u])); }
-    lo = (unsigned)l;
-    hi = std::min((unsigned)e, src_len);
+    taps_span(t.first.data(), t.taps.data(), src_len, a, b, lo, hi);
 }
 
 // [lx,hx) x [ly,hy) of the w x h plane that samples [x0,x1) x [y0,y1) of the Y path's dw x dh output depend on: the rect, +-2
@@ -29,12 +27,9 @@ inline void axis_source_span(int filter, unsigned dst_len, unsigned src_len, uns
 inline void y_path_rect_source_span(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, unsigned x0, unsigned y0, unsigned x1,
                                     unsigned y1, unsigned& lx, unsigned& hx, unsigned& ly, unsigned& hy)
 {
-    const unsigned cax = x0 >= 2 ? x0 - 2 : 0, cbx = std::min(dw, x1 + 2);
-    const unsigned uax = cax >= 4 ? cax - 4 : 0, ubx = std::min(dw, cbx + 4);
-    const unsigned cay = y0 >= 2 ? y0 - 2 : 0, cby = std::min(dh, y1 + 2);
-    const unsigned uay = cay >= 4 ? cay - 4 : 0, uby = std::min(dh, cby + 4);
-    axis_source_span(filter, dw, w, uax, ubx, lx, hx);
-    axis_source_span(filter, dh, h, uay, uby, ly, hy);
+    const HaloSpan vx = y_path_halo(dw, x0, x1), vy = y_path_halo(dh, y0, y1);
+    axis_source_span(filter, dw, w, vx.ua, vx.ub, lx, hx);
+    axis_source_span(filter, dh, h, vy.ua, vy.ub, ly, hy);
 }
 
 // chroma and alpha planes: nearest stays nearest, everything else is bilinear (as J.cfilter of srcnn_process_u8)

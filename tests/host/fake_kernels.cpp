@@ -8,7 +8,7 @@
 // closure whose footprint is refused does not run.  The contribution tables are read from (fake) device memory, which is what
 // checks the table uploads and the table cache's lifetimes.
 //
-// Resamplers and colour shell: the real arithmetic (fp64 weight x sample, fp64 adds, one fp32 store per pass, vertical pass
+// Resamplers (whole planes and the windows of the rect call) and colour shell: the real arithmetic (fp64 weight x sample, fp64 adds, one fp32 store per pass, vertical pass
 // first; the split and merge lines of the reference).
 // Layers: two bodies, fakek::set_layers():
 //   exact   the reference's tap order and roundings with the weights of oracle_get_weights: byte for byte the oracle.
@@ -505,12 +505,81 @@ void launch_layer3(const float* C2, size_t plane_stride, int W, int H, int c2_ro
     launch_conv3(C2, plane_stride, W, H, c2_row_base, c2_rows, out, out_row0, out_rows, relax, s);
 }
 
-// reached by no scenario of the harness (strict tier, no stage-level or rect call): defined for the link, loud if ever run
+// ---- the window kernels of the rect call (srcnn_window.h): the arithmetic of the two passes above, over a window ----
+
+// A strided block of w x rows floats is declared row by row: the floats between two rows belong to the caller (the canary columns
+// of a pitched destination) or to nobody (past the end of a window of the source), and the contract touches none of them.
+static void strided(Foot& f, const float* p, size_t stride, int w, int rows, const char* what, bool write = false)
+{
+    if (stride == (size_t)w) { f.range(p, sizeof(float) * (size_t)rows * w, what, write); return; }
+    for (int y = 0; y < rows && f.ok; ++y) f.range(p + (size_t)y * stride, sizeof(float) * (size_t)w, what, write);
+}
+
+void launch_window_rows(const float* src, size_t src_stride, int src_col_base, float* dst, int c0, int nc, int rows, const DevAxisTable& t, hipStream_t s)
+{
+    if (nc <= 0 || rows <= 0) return;
+    fakehip::enqueue(s, [=] {
+        Foot f{"window_rows"};
+        f.table(t, c0, c0 + nc, "table rows");
+        if (!f.ok) return;
+        int lo, hi;
+        span_of(t, c0, c0 + nc, lo, hi);
+        if (lo < src_col_base) { violation("window_rows: columns [%d, +%d) read source column %d below the base %d", c0, nc, lo, src_col_base); return; }
+        strided(f, src + (lo - src_col_base), src_stride, hi - lo, rows, "source columns");
+        f.range(dst, sizeof(float) * (size_t)rows * nc, "destination window", true);
+        if (!f.ok) return;
+        for (int y = 0; y < rows; ++y)
+            for (int xi = 0; xi < nc; ++xi) {
+                const int x = c0 + xi;
+                const float* in = src + (size_t)y * src_stride + (t.first[x] - src_col_base);
+                const double* wr = t.weight + (size_t)x * t.stride;
+                double acc = 0.0;
+                for (int k = 0; k < t.taps[x]; ++k) acc = acc + wr[k] * (double)in[k];
+                dst[(size_t)y * nc + xi] = (float)acc;
+            }
+    });
+}
+
+void launch_window_cols(const float* src, size_t src_stride, int src_row_base, float* dst, int nc, int r0, int rows, const DevAxisTable& t, hipStream_t s)
+{
+    if (nc <= 0 || rows <= 0) return;
+    fakehip::enqueue(s, [=] {
+        Foot f{"window_cols"};
+        f.table(t, r0, r0 + rows, "table rows");
+        if (!f.ok) return;
+        int lo, hi;
+        span_of(t, r0, r0 + rows, lo, hi);
+        if (lo < src_row_base) { violation("window_cols: rows [%d, +%d) read source row %d below the base %d", r0, rows, lo, src_row_base); return; }
+        strided(f, src + (size_t)(lo - src_row_base) * src_stride, src_stride, nc, hi - lo, "source rows");
+        f.range(dst, sizeof(float) * (size_t)rows * nc, "destination window", true);
+        if (!f.ok) return;
+        for (int ry = 0; ry < rows; ++ry) {
+            const int y = r0 + ry, s0 = t.first[y] - src_row_base, n = t.taps[y];
+            const double* wr = t.weight + (size_t)y * t.stride;
+            for (int xi = 0; xi < nc; ++xi) {
+                double acc = 0.0;
+                for (int k = 0; k < n; ++k) acc = acc + wr[k] * (double)src[(size_t)(s0 + k) * src_stride + xi];
+                dst[(size_t)ry * nc + xi] = (float)acc;
+            }
+        }
+    });
+}
+
+void launch_window_copy(const float* src, size_t src_stride, float* dst, size_t dst_stride, int w, int rows, hipStream_t s)
+{
+    if (w <= 0 || rows <= 0) return;
+    fakehip::enqueue(s, [=] {
+        Foot f{"window_copy"};
+        strided(f, src, src_stride, w, rows, "source window");
+        strided(f, dst, dst_stride, w, rows, "destination rows", true);
+        if (!f.ok) return;
+        for (int y = 0; y < rows; ++y) memcpy(dst + (size_t)y * dst_stride, src + (size_t)y * src_stride, sizeof(float) * (size_t)w);
+    });
+}
+
+// reached by no scenario of the harness (strict tier, no stage-level call): defined for the link, loud if ever run
 void launch_fused_f16(const float*, int, int, int, int, float*, int, int, const FusedF16Weights*, int, hipStream_t, unsigned long long*) { not_modelled("launch_fused_f16"); }
 void launch_conv1_planes(const float*, int, int, float*, hipStream_t) { not_modelled("launch_conv1_planes"); }
 void launch_conv2_planes(const float*, size_t, float*, hipStream_t) { not_modelled("launch_conv2_planes"); }
-void launch_window_rows(const float*, size_t, int, float*, int, int, int, const DevAxisTable&, hipStream_t) { not_modelled("launch_window_rows"); }
-void launch_window_cols(const float*, size_t, int, float*, int, int, int, const DevAxisTable&, hipStream_t) { not_modelled("launch_window_cols"); }
-void launch_window_copy(const float*, size_t, float*, size_t, int, int, hipStream_t) { not_modelled("launch_window_copy"); }
 
 }  // namespace srcnn

@@ -12,6 +12,8 @@
 // same pixel functions run over whole planes, single-threaded, with no bands, streams or staging (oracle resampler, oracle
 // colour lines).  Result buffers start as 0xFF, like every block of the fake runtime: a byte nobody wrote fails the comparison.
 // Every process must end with 0 violations of the fake runtime and, after srcnn_shutdown, an empty block registry.
+// Scenario `rect` runs the window route of the Y path (srcnn_y_path_rect_f32_dev: resample_window, the layers over a window,
+// the store of its interior) against the crop of the frame call's result, banded and not.
 //
 // The three suspects of ADVICE.md:
 //   suspect-a  REAL: host_is_page_locked() asked about the first byte only, so a buffer whose second half is pageable went to
@@ -49,6 +51,7 @@
 
 #include "../../include/libsrcnn_dropin.h"
 #include "../../include/srcnn_amd.h"
+#include "../../include/srcnn_amd_rect.h"
 
 namespace fakehip {
 unsigned long violations();
@@ -457,6 +460,91 @@ void scenario_suspect_c()      // FAKE_HIP_FAIL=hipMemcpyAsync:1 -- the fp16 wei
     small_case(13, 1, 3, 2.0f, fakek::kSparse);
 }
 
+// ---- 8. the rect route of the Y path (sparse) ----
+struct RectCase { unsigned x0, y0, rw, rh; bool tight; };
+
+// One rect of the dw x dh result into a destination of its own -- pitched, with two canary floats before and three after every
+// row, or tight -- against the crop of `whole`, the result of the frame call.
+void rect_case(const float* d_in, unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const RectCase& r, const std::vector<float>& whole)
+{
+    const size_t pitch = r.tight ? r.rw : r.rw + 5, lead = r.tight ? 0 : 2, n = pitch * r.rh + 8;
+    std::vector<float> canary(n), got(n);
+    for (size_t i = 0; i < n; ++i) canary[i] = -1000.f - (float)(i % 97);
+    float* d_out = (float*)srcnn_dev_alloc(n * sizeof(float));
+    CHECK(d_out != nullptr, "srcnn_dev_alloc");
+    if (!d_out) return;
+    CHECK(srcnn_memcpy_h2d(d_out, canary.data(), n * sizeof(float), nullptr) == 0, "h2d: %s", srcnn_last_error());
+    const int rc = srcnn_y_path_rect_f32_dev(d_in, 0, w, h, dw, dh, filter, r.x0, r.y0, r.rw, r.rh, d_out + lead, pitch * sizeof(float), nullptr);
+    CHECK(rc == 0, "rect %ux%u at (%u,%u) of %ux%u -> %d (%s)", r.rw, r.rh, r.x0, r.y0, dw, dh, rc, srcnn_last_error());
+    CHECK(srcnn_memcpy_d2h(got.data(), d_out, n * sizeof(float), nullptr) == 0, "d2h: %s", srcnn_last_error());
+    std::vector<float> want = canary;
+    for (unsigned y = 0; y < r.rh; ++y) memcpy(&want[lead + y * pitch], &whole[(size_t)(r.y0 + y) * dw + r.x0], r.rw * sizeof(float));
+    CHECK_SAME(got.data(), want.data(), n * sizeof(float), "rect %ux%u at (%u,%u) of %ux%u, filter %d: the crop of the frame, canaries untouched", r.rw, r.rh,
+               r.x0, r.y0, dw, dh, filter);
+    srcnn_dev_free(d_out);
+}
+
+// The frame call's result for a w x h plane (checked against the single-threaded reference), then every rect of `rects`.
+void rect_plane(unsigned w, unsigned h, unsigned dw, unsigned dh, int filter, const std::vector<RectCase>& rects)
+{
+    const std::vector<float> in = make_plane(w, h, w + dw);
+    std::vector<float> up((size_t)dw * dh), want((size_t)dw * dh), whole((size_t)dw * dh);
+    oracle_resample(in.data(), w, h, dw, dh, up.data(), filter);
+    fakek::layers_whole(up.data(), (int)dw, (int)dh, want.data(), fakek::kSparse);
+    memset(whole.data(), 0xFF, whole.size() * sizeof(float));
+    float* d_in = (float*)srcnn_dev_alloc(in.size() * sizeof(float));
+    float* d_whole = (float*)srcnn_dev_alloc(whole.size() * sizeof(float));
+    CHECK(d_in && d_whole, "srcnn_dev_alloc");
+    if (d_in && d_whole) {
+        CHECK(srcnn_memcpy_h2d(d_in, in.data(), in.size() * sizeof(float), nullptr) == 0, "h2d: %s", srcnn_last_error());
+        const int rc = srcnn_y_path_f32_dev(d_in, w, h, dw, dh, filter, d_whole, nullptr);
+        CHECK(rc == 0, "frame %ux%u -> %ux%u -> %d (%s)", w, h, dw, dh, rc, srcnn_last_error());
+        CHECK(srcnn_memcpy_d2h(whole.data(), d_whole, whole.size() * sizeof(float), nullptr) == 0, "d2h: %s", srcnn_last_error());
+        CHECK_SAME(whole.data(), want.data(), whole.size() * sizeof(float), "frame %ux%u -> %ux%u, filter %d", w, h, dw, dh, filter);
+        for (const RectCase& r : rects) rect_case(d_in, w, h, dw, dh, filter, r, whole);
+    }
+    srcnn_dev_free(d_in);
+    srcnn_dev_free(d_whole);
+}
+
+unsigned long long stage_launches(int stage)
+{
+    double ms = 0;
+    unsigned long long n = 0;
+    CHECK(srcnn_profile_read(stage, &ms, &n) == 0, "srcnn_profile_read: %s", srcnn_last_error());
+    return n;
+}
+
+void scenario_rect()
+{
+    fakek::set_layers(fakek::kSparse);
+    srcnn_profile_enable(1);      // the stage timers of the pass run too: one event pair per stage and pass
+    // 37 x 53 to 74 x 106 (bicubic) and to 55 x 79 (bilinear, not an integer ratio): the four corners, an interior rect, one sample,
+    // and a full-width rect with tight pitches (y_path_range's shortcut), in the same proportions on both
+    const struct { unsigned dw, dh; int filter; } outs[2] = {{74, 106, SRCNN_FILTER_BICUBIC}, {55, 79, SRCNN_FILTER_BILINEAR}};
+    for (const auto& o : outs) {
+        const unsigned dw = o.dw, dh = o.dh, cw = 9 * dw / 74, ch = 7 * dh / 106;
+        rect_plane(37, 53, dw, dh, o.filter,
+                   {{0, 0, cw, ch, false}, {dw - cw, 0, cw, ch, false}, {0, dh - ch, cw, ch, false}, {dw - cw, dh - ch, cw, ch, false},
+                    {23 * dw / 74, 40 * dh / 106, 20 * dw / 74, 11 * dh / 106, false}, {37 * dw / 74, 50 * dh / 106, 1, 1, false},
+                    {0, 30 * dh / 106, dw, 10 * dh / 106, true}});
+    }
+    // one frame pass and one pass per rect, each with its three stages
+    for (int st = 0; st < SRCNN_STAGE_COUNT; ++st) CHECK(stage_launches(st) == 2 * 8, "stage %d ran %llu times, not 16", st, stage_launches(st));
+    // Bands.  The limit cannot go below 1 MiB, where a 74-wide window still holds all its rows: the 16-row floor of the band
+    // function needs 32 * 4 * Ww * 20 bytes above 1 MiB, a window of 410 floats or more.  So a wide, flat plane of its own, 280 x 28
+    // to 560 x 56 and to 420 x 42, and rects 40 rows high and at least 410 wide: three bands of 16, 16 and 8 rows, through the window
+    // route (left border, right border, interior) and through y_path_range (full width, tight)
+    const size_t before = srcnn_set_workspace_limit(1u << 20);
+    srcnn_profile_reset();
+    rect_plane(280, 28, 560, 56, SRCNN_FILTER_BICUBIC, {{0, 8, 415, 40, false}, {140, 16, 420, 40, false}, {70, 3, 430, 40, false}, {0, 9, 560, 40, true}});
+    rect_plane(280, 28, 420, 42, SRCNN_FILTER_BILINEAR, {{0, 1, 412, 40, false}, {7, 2, 413, 40, false}, {0, 0, 420, 40, true}});
+    // the frames: 56 rows in four bands, 42 in three; every rect in three
+    for (int st = 0; st < SRCNN_STAGE_COUNT; ++st) CHECK(stage_launches(st) == 4 + 3 + 7 * 3, "stage %d ran %llu times under the 1 MiB limit, not 28", st, stage_launches(st));
+    srcnn_set_workspace_limit(before);
+    srcnn_profile_enable(0);
+}
+
 struct Scenario { const char* name; const char* env; std::function<void()> run; };
 const std::vector<Scenario>& scenarios()
 {
@@ -472,6 +560,7 @@ const std::vector<Scenario>& scenarios()
         {"async-chain-1", "SRCNN_ASYNC_CHAIN=1", scenario_async},
         {"async-chain-2", "SRCNN_ASYNC_CHAIN=2", scenario_async},
         {"stream", "", scenario_stream},
+        {"rect", "", scenario_rect},
         {"multi", "SRCNN_DEVICES=0,0,0", scenario_multi},
         {"lifecycle", "", scenario_lifecycle},
         {"suspect-a", "", scenario_suspect_a},

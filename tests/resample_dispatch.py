@@ -5,12 +5,12 @@ tests/test_gpu_colour_shell.py are checked against it on the CPU (tests/test_res
 result is compared with the oracle bit for bit.  It reads the product's own axis tables through srcnn_axis_table (host code:
 no device needed) and mirrors, line for line:
 
-  resample_src_rows       libsrcnn_amd/csrc/srcnn_capi.cpp:809-873     the plane-resample branches
+  resample_src_rows       libsrcnn_amd/csrc/srcnn_capi.cpp (resample_src_rows)   the plane-resample branches
   rs2d_plan               libsrcnn_amd/csrc/srcnn_kernels.hip:1398-1427 MAXT, LW, patch rows, LDS, grid
   rs2d_fits               libsrcnn_amd/csrc/srcnn_kernels.hip:1467-1472
   launch_rs2d             libsrcnn_amd/csrc/srcnn_kernels.hip:1474-1501 DMA form, vec flag
   launch_merge_fused      libsrcnn_amd/csrc/srcnn_kernels.hip:1503-1521
-  get_table (monotone)    libsrcnn_amd/csrc/srcnn_capi.cpp:426-435
+  get_table (monotone)    libsrcnn_amd/csrc/srcnn_capi.cpp (get_table)
   process_share           libsrcnn_amd/csrc/srcnn_pipeline.cpp:389-436  fused or plane shell, buffer offsets
   launch_rgb_split / launch_ycc_merge   srcnn_kernels.hip:1699-1747   4-pixel forms and scalar tails
 
@@ -59,7 +59,7 @@ class Table:
         self.taps = np.minimum(right.astype(np.int64) - left + 1, window)           # resample_table.hpp:126-129
         self.end = self.first + self.taps
         self.max_taps = int(self.taps.max())
-        self.monotone = bool(np.all(np.diff(self.first) >= 0) and np.all(np.diff(self.end) >= 0))   # srcnn_capi.cpp:433-435
+        self.monotone = bool(np.all(np.diff(self.first) >= 0) and np.all(np.diff(self.end) >= 0))   # get_table, srcnn_capi.cpp
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,7 +115,7 @@ def rs2d_cell(p, dma, vec):
 
 def plane_cell(filt, sw, sh, dw, dh, settings=DEFAULT, dst_aligned16=True, r0=0, r1=None):
     """The kernel(s) srcnn_resample_f32_dev / the Y path's resample of a float plane runs for destination rows [r0, r1)
-    (resample_src_rows, srcnn_capi.cpp:809-873).  dst_aligned16: the destination pointer is 16-byte aligned."""
+    (resample_src_rows of srcnn_capi.cpp).  dst_aligned16: the destination pointer is 16-byte aligned."""
     r1 = dh if r1 is None else r1
     if sw == dw and sh == dh:
         return "identity"
