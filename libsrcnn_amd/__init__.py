@@ -76,7 +76,10 @@ YUV_PACKED_RECT_LIST_SYMBOLS = ["srcnn_yuv_packed_rect_list_abi_version", "srcnn
 # only what changed between two Y frames (include/srcnn_amd_delta.h, listed in include/srcnn_amd_delta.abi; its own version)
 DELTA_SYMBOLS = ["srcnn_delta_abi_version", "srcnn_y_path_delta_grid", "srcnn_y_path_delta_flags_dev", "srcnn_y_path_delta_rects",
                  "srcnn_y_path_delta_f32_dev"]
-C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS   # everything the library exports besides the two C++ symbols
+# only what changed between two RGB(A) images (include/srcnn_amd_rgb_delta.h, listed in include/srcnn_amd_rgb_delta.abi; its own version)
+RGB_DELTA_SYMBOLS = ["srcnn_rgb_delta_abi_version", "srcnn_rgb_delta_grid", "srcnn_rgb_delta_flags_dev", "srcnn_rgb_delta_rects",
+                     "srcnn_rgb_upscale_delta_dev"]
+C_ABI_SYMBOLS = STABLE_ABI_SYMBOLS + DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS + RGB_DELTA_SYMBOLS   # everything the library exports besides the two C++ symbols
 CXX_SYMBOLS = ["_Z20ConfigureFilterSRCNN15SRCNNFilterTypeb", "_Z12ProcessSRCNNPKhjjjfRPhRjPS1_Pj"]
 
 
@@ -237,9 +240,15 @@ def lib():
             "srcnn_y_path_delta_flags_dev": (i, [vp, sz, vp, sz, u, u, u, u, i, u, u, vp, vp]),
             "srcnn_y_path_delta_rects": (i, [vp, u, u, u, u, u, u, vp, sz, vp, u, C.POINTER(u)]),
             "srcnn_y_path_delta_f32_dev": (i, [vp, sz, vp, sz, u, u, u, u, i, u, u, vp, sz, vp, C.POINTER(DeltaStats)]),
+            "srcnn_rgb_delta_abi_version": (i, []),
+            "srcnn_rgb_delta_grid": (i, [u, u, f, i, u, u, C.POINTER(u), C.POINTER(u), C.POINTER(u), C.POINTER(u)]),
+            "srcnn_rgb_delta_flags_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), u, u, vp, vp]),
+            "srcnn_rgb_delta_rects": (i, [vp, u, u, u, u, C.POINTER(RgbFormat), u, u, C.POINTER(vp), C.POINTER(sz), vp, sz, vp, u, u, C.POINTER(u)]),
+            "srcnn_rgb_upscale_delta_dev": (i, [C.POINTER(RgbFormat), u, u, f, i, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), u, u,
+                                                C.POINTER(vp), C.POINTER(sz), vp, sz, vp, C.POINTER(DeltaStats)]),
         }
         for name, (res, args) in sig.items():
-            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
+            if name in DEBUG_SYMBOLS + YUV_SYMBOLS + YUV_EX_SYMBOLS + RGB_SYMBOLS + YUV_PACKED_SYMBOLS + RECT_SYMBOLS + RGB_RECT_SYMBOLS + YUV_RECT_SYMBOLS + YUV_PACKED_RECT_SYMBOLS + RECT_LIST_SYMBOLS + RGB_RECT_LIST_SYMBOLS + YUV_RECT_LIST_SYMBOLS + YUV_PACKED_RECT_LIST_SYMBOLS + DELTA_SYMBOLS + RGB_DELTA_SYMBOLS and not hasattr(L, name) and os.environ.get("SRCNN_AMD_LIB"):
                 continue                  # an older build loaded for an A/B run (tools/lib_ab.py): it may lack newer entry points
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
@@ -1238,6 +1247,108 @@ def rgb_upscale_rects(image, rects, multiply=2.0, filt=SRCNNF_Bicubic, layout=No
     return res
 
 
+def _four(xs, kind, fill):
+    """A ctypes array of 4 plane arguments (kind c_void_p, see _addr) or pitches (kind c_size_t), or None for None."""
+    if xs is None:
+        return None
+    xs = list(xs) + [fill] * (4 - len(xs))
+    return (kind * 4)(*[(_addr(x) if kind is C.c_void_p else int(x or 0)) for x in xs])
+
+
+def rgb_delta_grid(w, h, multiply, filt, tile=(0, 0)):
+    """(dw, dh, cols, rows): the output size and the tile grid of the RGB(A) delta call (srcnn_rgb_delta_grid; no device).
+    tile: (tile_w, tile_h), 0 = the default 64."""
+    r = [C.c_uint(0) for _ in range(4)]
+    check(lib().srcnn_rgb_delta_grid(int(w), int(h), float(np.float32(multiply)), int(filt), int(tile[0]), int(tile[1]), *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+def rgb_delta_flags_dev(fmt, w, h, multiply, filt, prev, prev_pitch, cur, cur_pitch, tile, flags, stream=None):
+    """srcnn_rgb_delta_flags_dev on device memory, as given: prev (None = no previous image) / cur are up to 4 plane arguments of
+    whole source images (see _addr), pitches byte counts or None (tight), flags receives cols x rows bytes.  Asynchronous on
+    `stream`."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    check(lib().srcnn_rgb_delta_flags_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                          _four(prev, C.c_void_p, None), _four(prev_pitch, C.c_size_t, 0), _four(cur, C.c_void_p, None),
+                                          _four(cur_pitch, C.c_size_t, 0), int(tile[0]), int(tile[1]), _addr(flags), handle))
+
+
+def rgb_delta_rects(flags, tile, fmt, dw, dh, dst=None, dst_pitch=None, dst_conv=None, dst_conv_pitch=0, cap=None, item_size=None):
+    """srcnn_rgb_delta_rects (pure host): the coalescer over a (rows, cols) uint8 array of flags of tile[0] x tile[1] tiles, as
+    items that point into the full-size image dst / dst_conv (plane arguments, or None).  Returns
+    [(x0, y0, rw, rh, [dst 0..3], [dst_pitch 0..3], dst_conv, dst_conv_pitch)].  cap: None = as many items as needed; 0 = count
+    only (returns the number); anything else is the capacity handed to the call (tests)."""
+    flags = np.ascontiguousarray(flags, np.uint8)
+    rows, cols = flags.shape
+    n = C.c_uint(0)
+    size = C.sizeof(RgbRectItem) if item_size is None else int(item_size)
+    args = (flags.ctypes.data, cols, rows, int(tile[0]), int(tile[1]), C.byref(fmt) if fmt is not None else None, int(dw), int(dh),
+            _four(dst, C.c_void_p, None), _four(dst_pitch, C.c_size_t, 0), _addr(dst_conv), int(dst_conv_pitch or 0))
+    if cap is None or cap == 0:
+        check(lib().srcnn_rgb_delta_rects(*args, None, 0, size, C.byref(n)))
+        if cap == 0:
+            return n.value
+        cap = n.value
+    arr = (RgbRectItem * max(1, int(cap)))()
+    check(lib().srcnn_rgb_delta_rects(*args, C.cast(arr, C.c_void_p), int(cap), size, C.byref(n)))
+    return [(a.x0, a.y0, a.rw, a.rh, list(a.dst), list(a.dst_pitch), a.dst_conv, a.dst_conv_pitch) for a in arr[:n.value]]
+
+
+def rgb_upscale_delta_dev(fmt, w, h, multiply, filt, prev, prev_pitch, cur, cur_pitch, tile, dst, dst_pitch, dst_conv=None, dst_conv_pitch=0,
+                          stream=None, stats=True, struct_size=None):
+    """srcnn_rgb_upscale_delta_dev on device memory, as given: repaints inside the full-size image dst (and dst_conv) what can
+    differ between prev (None = no previous image) and cur.  Blocks until the flags have arrived; the upscale is asynchronous on
+    `stream`.  Returns the DeltaStats (None with stats=False)."""
+    handle = stream.handle if isinstance(stream, Stream) else stream
+    st = None
+    if stats:
+        st = DeltaStats()
+        st.struct_size = C.sizeof(DeltaStats) if struct_size is None else int(struct_size)
+    check(lib().srcnn_rgb_upscale_delta_dev(C.byref(fmt) if fmt is not None else None, int(w), int(h), float(np.float32(multiply)), int(filt),
+                                            _four(prev, C.c_void_p, None), _four(prev_pitch, C.c_size_t, 0), _four(cur, C.c_void_p, None),
+                                            _four(cur_pitch, C.c_size_t, 0), int(tile[0]), int(tile[1]), _four(dst, C.c_void_p, None),
+                                            _four(dst_pitch, C.c_size_t, 0), _addr(dst_conv), int(dst_conv_pitch or 0), handle,
+                                            C.byref(st) if st is not None else None))
+    return st
+
+
+def rgb_upscale_delta(prev, cur, out, multiply=2.0, filt=SRCNNF_Bicubic, layout=None, order="rgb", depth=None, tile=(0, 0), conv=None):
+    """numpy convenience over srcnn_rgb_upscale_delta_dev: `out` (rgb_upscale of `prev`; prev None = anything) is updated to
+    rgb_upscale of `cur`, and so is `conv` (the truncated Y' plane) when given.  Images as for rgb_upscale.  Returns
+    (out, stats), or (out, conv, stats) with conv -- new arrays; what the call did not repaint is copied from `out` / `conv`."""
+    image = np.asarray(cur)
+    if image.ndim != 3:
+        raise ValueError("an RGB(A) image is (h, w, c) or (c, h, w), not %r" % (image.shape,))
+    if layout is None:
+        layout = "interleaved" if image.shape[2] in (3, 4) else "planar"
+    planar = _RGB_LAYOUTS.get(layout.lower() if isinstance(layout, str) else layout, layout) == RGB_PLANAR
+    if depth is None:
+        depth = 8 if image.dtype == np.uint8 else 16
+    dt = np.uint8 if depth == 8 else np.uint16
+    image = np.ascontiguousarray(image, dt)
+    (c, h, w) = image.shape if planar else (image.shape[2], image.shape[0], image.shape[1])
+    if c not in (3, 4):
+        raise ValueError("%d channels: an RGB(A) image has 3 or 4" % c)
+    dw, dh = output_size(w, h, multiply)
+    o = np.ascontiguousarray(out, dt)
+    if o.shape != ((c, dh, dw) if planar else (dh, dw, c)):
+        raise ValueError("out is %r, the output image %r" % (o.shape, (c, dh, dw) if planar else (dh, dw, c)))
+    if prev is not None and np.asarray(prev).shape != image.shape:
+        raise ValueError("prev is %r, cur %r" % (np.asarray(prev).shape, image.shape))
+    fmt = rgb_format(RGB_PLANAR if planar else RGB_INTERLEAVED, order, c == 4, depth)
+    bps = np.dtype(dt).itemsize
+    planes = lambda buf, pw, ph: [(buf, k * pw * ph * bps) for k in range(c)] if planar else [buf]   # noqa: E731
+    dprev = DeviceBuffer.from_numpy(np.ascontiguousarray(prev, dt)) if prev is not None else None
+    dcur = DeviceBuffer.from_numpy(image)
+    dout = DeviceBuffer.from_numpy(o)
+    dconv = DeviceBuffer.from_numpy(np.ascontiguousarray(conv, dt).reshape(dh, dw)) if conv is not None else None
+    st = rgb_upscale_delta_dev(fmt, w, h, multiply, filt, planes(dprev, w, h) if dprev is not None else None, None, planes(dcur, w, h), None,
+                               tile, planes(dout, dw, dh), None, dconv, 0)
+    sync()
+    res = dout.to_numpy(dt, o.shape)
+    return (res, dconv.to_numpy(dt, (dh, dw)), st) if conv is not None else (res, st)
+
+
 def yuv_rect_items(items):
     """A ctypes array of srcnn_yuv_rect_item from (x0, y0, rw, rh[, dst[, dst_pitch]]) tuples, or `items` itself when it already
     is such an array.  dst: up to 3 plane arguments (each a DeviceBuffer, a (DeviceBuffer, byte offset) pair or an address;
@@ -1564,6 +1675,39 @@ def rgb_upscale_rect_list_torch(t, rects, out, multiply=2.0, filt=SRCNNF_Bicubic
     stream = torch.cuda.current_stream(t.device).cuda_stream
     rgb_upscale_rect_list_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, src, [sh * bps] * len(src), items, stream or None)
     return out
+
+
+def rgb_upscale_delta_torch(prev, cur, out, multiply=2.0, filt=SRCNNF_Bicubic, order="rgb", depth=None, tile=(0, 0)):
+    """srcnn_rgb_upscale_delta_dev on torch tensors that live on a GPU: `out`, which holds rgb_upscale_torch(prev, ...), is updated
+    in place to rgb_upscale_torch(cur, ...) by repainting only the tiles that can differ.  cur as for rgb_upscale_torch; prev is
+    None (no previous image: everything is repainted) or a tensor of cur's shape, dtype, device and memory layout (its row
+    padding may differ); out is a full-size dw x dh image tensor of cur's dtype, shape order and memory layout (rows may be
+    padded): it is written through its strides and nothing of a clean tile is touched.  The call waits once, for the tile flags,
+    on torch.cuda.current_stream(), and queues the repaint there.  Returns the DeltaStats."""
+    W, H, Cn, bps, depth, hwc, layout, sh, sc = _rgb_torch_layout(cur, depth, "rgb_upscale_delta_torch")
+    import torch
+    _rgb_torch_context(cur)
+    dw, dh = output_size(W, H, multiply)
+    planes = lambda t, chan: [t.data_ptr()] if layout == RGB_INTERLEAVED else [t.data_ptr() + k * chan * bps for k in range(Cn)]   # noqa: E731
+    p_src = p_pitch = None
+    if prev is not None:
+        if not isinstance(prev, torch.Tensor) or prev.device != cur.device or prev.dtype != cur.dtype:
+            raise ValueError("prev must be a tensor of %s on %s" % (cur.dtype, cur.device))
+        pW, pH, pC, _, _, phwc, playout, psh, psc = _rgb_torch_layout(prev, depth, "rgb_upscale_delta_torch(prev)")
+        if (pW, pH, pC, phwc, playout) != (W, H, Cn, hwc, layout):
+            raise ValueError("prev is %d x %d x %d, cur %d x %d x %d in another layout or shape order" % (pW, pH, pC, W, H, Cn))
+        p_src = planes(prev, psc)
+        p_pitch = [psh * bps] * len(p_src)
+    if not isinstance(out, torch.Tensor) or out.device != cur.device or out.dtype != cur.dtype:
+        raise ValueError("out must be a tensor of %s on %s" % (cur.dtype, cur.device))
+    oW, oH, oC, _, _, ohwc, olayout, osh, osc = _rgb_torch_layout(out, depth, "rgb_upscale_delta_torch(out)")
+    if (oW, oH, oC, ohwc, olayout) != (dw, dh, Cn, hwc, layout):
+        raise ValueError("out is %d x %d x %d (%s), the output image %d x %d x %d in the layout of cur" %
+                         (oW, oH, oC, "interleaved" if olayout == RGB_INTERLEAVED else "planar", dw, dh, Cn))
+    src, dst = planes(cur, sc), planes(out, osc)
+    stream = torch.cuda.current_stream(cur.device).cuda_stream
+    return rgb_upscale_delta_dev(rgb_format(layout, order, Cn == 4, depth), W, H, multiply, filt, p_src, p_pitch, src, [sh * bps] * len(src), tile,
+                                 dst, [osh * bps] * len(dst), None, 0, stream or None)
 
 
 class PinnedArray:

@@ -150,4 +150,158 @@ void launch_delta_flags(const float* d_prev, size_t prev_pitch, const float* d_c
     else hipLaunchKernelGGL((k_delta_flags<false>), g, dim3(kDeltaThreads), lds, s, p, prev_pitch, q, cur_pitch, w, pieces, items, d_spans, cols, rows, d_flags);
 }
 
+// =====================================================================================================================
+// k_delta_flags_bytes
+// =====================================================================================================================
+// The same pass over integer pixel surfaces (include/srcnn_amd_rgb_delta.h): up to four planes that share one pixel grid, one pair
+// of span tables (in PIXELS) and one set of hit bytes.  Comparison is on bytes; a pixel is bpp consecutive bytes of a plane's row
+// (3, 4, 6 or 8 interleaved, 1 or 2 planar), so the pixel of byte b of a row is b / bpp, whatever word, chunk or piece b is in.
+// A work item is one piece of one row of one plane, items = planes * h * pieces, workgroups stride over them.  A chunk is 16
+// bytes; a lane compares U chunks, 256 lanes apart; a piece is 256 * U chunks.
+//
+// The piece.  These rows are short next to the float plane's: 11 520 B (720 chunks) for 3840 RGB8 pixels, 15 360 B (960) for
+// BGRA, 5 760 B (360) for 1920 RGB8.  A fixed piece of 1024 chunks would leave 30 % of the lanes of every RGB8 item without a
+// chunk, a fixed piece of 256 would leave the 960-chunk row with two loads in flight per lane where eight fit.  So U is a
+// template parameter, 1 ... 4, and the launcher takes the U that pads the row's chunks least and, among those, the largest:
+// 720 -> U = 3 (768), 960 -> U = 4 (1024), 360 -> U = 2 (512), 480 -> U = 2 (512), 240 -> U = 1 (256).
+//
+// VEC (every base and, with more than one row, every pitch of the launch a multiple of 16, row_bytes >= 16): a whole chunk is one 16-byte load per image, all
+// 2 * U of them unconditional -- a lane whose chunk lies past the row's last whole chunk reads that one again and drops it -- and
+// in flight before the first compare; the row's last row_bytes % 16 bytes are read by the one lane whose chunk they would be,
+// in words and then bytes.  Otherwise (depth 8 allows odd bases and pitches) every byte is a load of its own, clamped to the
+// row's last byte: correct at any alignment, one instance (U = 1), not fast.  Nothing past a row's row_bytes is ever read.
+//
+// Exactness.  The clean path ORs the XORs of a chunk's four words.  A chunk that differs is taken apart into a mask of its
+// differing BYTES; every such byte's pixel, b / bpp (a division, on this rare path), gets its tile columns marked.  A pixel that
+// merely shares a word or a chunk with a differing byte is not marked; a pixel that straddles a word, a chunk or a piece is
+// marked by whichever lane or item sees one of its bytes differ, to the same columns.  Rows, flag stores and the hit bytes are
+// k_delta_flags's.
+__device__ __forceinline__ unsigned delta_byte_mask(unsigned x)          // bit j: byte j of the word is not 0
+{
+    return (x & 0xffu ? 1u : 0u) | (x & 0xff00u ? 2u : 0u) | (x & 0xff0000u ? 4u : 0u) | (x & 0xff000000u ? 8u : 0u);
+}
+
+template <bool VEC, int U>
+__global__ __launch_bounds__(kDeltaThreads) void k_delta_flags_bytes(const DeltaBytePlanes P, unsigned pieces, unsigned items,
+                                                                      const unsigned* __restrict__ spans, unsigned cols, unsigned rows,
+                                                                      unsigned char* __restrict__ flags)
+{
+    extern __shared__ unsigned s_tab[];                   // xlo[cols], xhi[cols], ylo[rows], yhi[rows], then a hit byte per column
+    const unsigned* xlo = s_tab;
+    const unsigned* xhi = xlo + cols;
+    const unsigned* ylo = xhi + cols;
+    const unsigned* yhi = ylo + rows;
+    unsigned char* hit = reinterpret_cast<unsigned char*>(s_tab + 2 * (cols + rows));
+    const unsigned tid = threadIdx.x;
+    for (unsigned i = tid; i < 2 * (cols + rows); i += kDeltaThreads) s_tab[i] = spans[i];
+    for (unsigned i = tid; i < cols; i += kDeltaThreads) hit[i] = 0;
+    __syncthreads();
+
+    const unsigned whole = P.row_bytes / 16, tail = P.row_bytes % 16;      // whole chunks of a row, bytes of its partial chunk
+    const unsigned per_plane = P.rows * pieces;
+    for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
+        const unsigned plane = item / per_plane, in_plane = item - plane * per_plane;
+        const unsigned y = in_plane / pieces, piece = in_plane - y * pieces;
+        const unsigned char* p = P.prev[plane] + (size_t)y * P.prev_pitch[plane];
+        const unsigned char* q = P.cur[plane] + (size_t)y * P.cur_pitch[plane];
+        const unsigned ch0 = piece * (unsigned)(U * kDeltaThreads) + tid;
+        unsigned long long mm = 0;                        // bit 16 * u + j: byte j of chunk u differs
+        if constexpr (VEC) {
+            uint4 a[U], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned ch = min(ch0 + (unsigned)u * kDeltaThreads, whole - 1);      // (row_bytes >= 16: the launcher)
+                a[u] = *reinterpret_cast<const uint4*>(p + 16 * (size_t)ch);
+                b[u] = *reinterpret_cast<const uint4*>(q + 16 * (size_t)ch);
+            }
+            unsigned d = 0;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned x = (a[u].x ^ b[u].x) | (a[u].y ^ b[u].y) | (a[u].z ^ b[u].z) | (a[u].w ^ b[u].w);
+                d |= ch0 + (unsigned)u * kDeltaThreads < whole ? x : 0u;
+            }
+            if (d) {                                      // (rare: which bytes)
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const unsigned m = delta_byte_mask(a[u].x ^ b[u].x) | delta_byte_mask(a[u].y ^ b[u].y) << 4 |
+                                       delta_byte_mask(a[u].z ^ b[u].z) << 8 | delta_byte_mask(a[u].w ^ b[u].w) << 12;
+                    if (ch0 + (unsigned)u * kDeltaThreads < whole) mm |= (unsigned long long)m << (16 * u);
+                }
+            }
+        } else {
+            unsigned char a[U][16], b[U][16];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const unsigned at = min(16 * (ch0 + (unsigned)u * kDeltaThreads) + (unsigned)j, P.row_bytes - 1);
+                    a[u][j] = p[at];
+                    b[u][j] = q[at];
+                }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (16 * (ch0 + (unsigned)u * kDeltaThreads) + (unsigned)j < P.row_bytes && a[u][j] != b[u][j]) mm |= 1ull << (16 * u + j);
+        }
+        int any = mm != 0;
+        unsigned last = ~0u;                              // (bytes of one pixel follow each other: one mark per pixel)
+        while (mm) {                                      // (rare, and not unrolled: the clean path is a branch over it)
+            const unsigned bit = (unsigned)__ffsll((long long)mm) - 1u;
+            mm &= mm - 1ull;
+            const unsigned x = (16 * (ch0 + (bit >> 4) * kDeltaThreads) + (bit & 15u)) / P.bpp;
+            if (x != last) delta_mark(xlo, xhi, cols, x, hit);
+            last = x;
+        }
+        if constexpr (VEC) {                              // the row's partial chunk, for the lane whose chunk it would be
+            if (tail && whole >= piece * (unsigned)(U * kDeltaThreads) && whole < (piece + 1) * (unsigned)(U * kDeltaThreads) &&
+                (whole - ch0) % kDeltaThreads == 0) {
+                const unsigned at = 16 * whole;           // (a multiple of 16 from a 16-byte aligned row: words are aligned)
+                unsigned k = 0;
+                for (; k + 4 <= tail; k += 4) {
+                    const unsigned m = delta_byte_mask(*reinterpret_cast<const unsigned*>(p + at + k) ^ *reinterpret_cast<const unsigned*>(q + at + k));
+                    for (unsigned j = 0; j < 4; ++j)
+                        if (m >> j & 1u) { any = 1; delta_mark(xlo, xhi, cols, (at + k + j) / P.bpp, hit); }
+                }
+                for (; k < tail; ++k)
+                    if (p[at + k] != q[at + k]) { any = 1; delta_mark(xlo, xhi, cols, (at + k) / P.bpp, hit); }
+            }
+        }
+        if (__syncthreads_or(any)) {                      // the same answer in every lane
+            const unsigned r1 = delta_count_le(ylo, rows, y);
+            const unsigned r0 = delta_count_le(yhi, rows, y);
+            for (unsigned c = tid; c < cols; c += kDeltaThreads) {
+                if (!hit[c]) continue;
+                hit[c] = 0;
+                for (unsigned r = r0; r < r1; ++r) flags[(size_t)r * cols + c] = 1;
+            }
+            __syncthreads();                              // the hit bytes are clear before the next item marks them
+        }
+    }
+}
+
+void launch_delta_flags_bytes(const DeltaBytePlanes& P, const unsigned* d_spans, unsigned cols, unsigned rows, unsigned char* d_flags, hipStream_t s)
+{
+    (void)hipMemsetAsync(d_flags, 0, (size_t)cols * rows, s);
+    bool vec = P.row_bytes >= 16;
+    for (unsigned k = 0; k < P.planes; ++k)
+        vec = vec && aligned_to(P.prev[k], 16) && aligned_to(P.cur[k], 16) &&
+              (P.rows == 1 || (P.prev_pitch[k] % 16 == 0 && P.cur_pitch[k] % 16 == 0));      // (one row: the pitch places nothing)
+    const unsigned chunks = (P.row_bytes + 15) / 16;
+    unsigned unroll = 1, padded = ~0u;                    // the U that pads the row least; among those the largest
+    for (unsigned u = 1; vec && u <= 4; ++u) {
+        const unsigned span = u * kDeltaThreads, n = (chunks + span - 1) / span * span;
+        if (n <= padded) { padded = n; unroll = u; }
+    }
+    const unsigned pieces = (chunks + unroll * kDeltaThreads - 1) / (unroll * kDeltaThreads);
+    const unsigned items = P.planes * P.rows * pieces;    // (row_bytes * rows < 2^34 over all planes: under 2^23)
+    const size_t lds = sizeof(unsigned) * delta_span_words(cols, rows) + ((size_t)cols + 3) / 4 * 4;
+    const dim3 g(std::min(items, kDeltaGridCap)), b(kDeltaThreads);
+    if (!vec) hipLaunchKernelGGL((k_delta_flags_bytes<false, 1>), g, b, lds, s, P, pieces, items, d_spans, cols, rows, d_flags);
+    else if (unroll == 1) hipLaunchKernelGGL((k_delta_flags_bytes<true, 1>), g, b, lds, s, P, pieces, items, d_spans, cols, rows, d_flags);
+    else if (unroll == 2) hipLaunchKernelGGL((k_delta_flags_bytes<true, 2>), g, b, lds, s, P, pieces, items, d_spans, cols, rows, d_flags);
+    else if (unroll == 3) hipLaunchKernelGGL((k_delta_flags_bytes<true, 3>), g, b, lds, s, P, pieces, items, d_spans, cols, rows, d_flags);
+    else hipLaunchKernelGGL((k_delta_flags_bytes<true, 4>), g, b, lds, s, P, pieces, items, d_spans, cols, rows, d_flags);
+}
+
 }  // namespace srcnn

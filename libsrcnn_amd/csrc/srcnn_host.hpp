@@ -107,7 +107,7 @@ struct Scratch {            // the buffers of a Workspace: movable, so that a wo
 struct DeltaStage {
     PinnedBuf pin;
     bool valid = false;
-    unsigned key[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // w, h, dw, dh, filter, tile_w, tile_h, 0
+    unsigned key[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // w, h, dw, dh, filter, tile_w, tile_h, whose: 0 = the Y call's tables, 1 = the RGB(A) call's
 };
 // Page-locked staging of the rect list call's descriptor tables.  A call fills the next slot of the ring on the host, queues the
 // copy to Scratch::list on its stream and records the slot's event behind it; a slot is written again only after that event has

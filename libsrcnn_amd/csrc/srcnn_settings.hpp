@@ -51,7 +51,7 @@
     X(B, rgb_rect_list_unfused, "SRCNN_RGB_RECT_LIST_UNFUSED", 0, "0/1", "RGB(A) rect list call: every item as a single RGB(A) rect call instead of small rects sharing one atlas per layer launch, with Y read and colour merged by `k_rgb_list_resample` / `k_rgb_list_merge`") \
     X(B, yuv_rect_list_unfused, "SRCNN_YUV_RECT_LIST_UNFUSED", 0, "0/1", "planar / semi-planar YUV rect list call: every item as a single YUV rect call instead of small rects sharing one atlas per layer launch, with luma read and written by `k_yuv_list_resample` / `k_yuv_list_luma` and chroma by `k_yuv_list_chroma`") \
     X(B, yuv_packed_rect_list_unfused, "SRCNN_YUV_PACKED_RECT_LIST_UNFUSED", 0, "0/1", "packed YUV rect list call: every item as a single packed YUV rect call instead of small rects sharing one atlas per layer launch, with luma read by `k_yuvp_list_resample` and chroma / alpha resampled, merged with Y' and stored by `k_yuvp_list_merge`") \
-    X(I, delta_whole_permille, "SRCNN_DELTA_WHOLE_PERMILLE", 850, "permille of `dw * dh`", "delta call (`srcnn_y_path_delta_f32_dev`): the frame is repainted as one rect instead of the coalesced dirty rects when the sum of their cells, (rw + 12) x (rh + 12), reaches this share of the output frame.  Started at 1000, where the list certainly does more layer work than the frame; `profiles/delta_probe.txt` measures the crossover on a 3840x2160 -> 7680x4320 frame: at 0.867 (one block of 85 % of the tiles) the list route still beats the whole frame by 10 %, at 0.877 (a random 70 % of the tiles, 1693 rects) it is 1.5 % behind -- rounded down to 50, never below 500.  Either route gives the same bits")
+    X(I, delta_whole_permille, "SRCNN_DELTA_WHOLE_PERMILLE", 850, "permille of `dw * dh`", "delta calls (`srcnn_y_path_delta_f32_dev`, `srcnn_rgb_upscale_delta_dev`): the frame is repainted as one rect instead of the coalesced dirty rects when the sum of their cells, (rw + 12) x (rh + 12), reaches this share of the output frame.  Started at 1000; `profiles/delta_probe.txt` (Y) and `profiles/rgb_delta_probe.txt` (8-bit RGB, BGRA) measure the same crossover on 3840x2160 -> 7680x4320: at 0.867 the list route is still ahead of the whole frame, at 0.877 behind -- rounded down to 50, never below 500; the RGB(A) call has no setting of its own.  Either route gives the same bits")
 
 namespace srcnn {
 
