@@ -39,7 +39,7 @@ else
 SRCS    := srcnn_kernels.hip srcnn_fused_f16.hip srcnn_yuv_planes.hip srcnn_yuv_packed.hip srcnn_rgb.hip srcnn_rgb_window.hip srcnn_yuv_window.hip srcnn_yuv_packed_window.hip srcnn_window.hip srcnn_rect_list.hip srcnn_rgb_rect_list.hip srcnn_yuv_rect_list.hip srcnn_yuv_packed_rect_list.hip srcnn_delta.hip srcnn_rect_list_call.cpp srcnn_rgb_rect_list_call.cpp srcnn_yuv_rect_list_call.cpp srcnn_yuv_packed_rect_list_call.cpp srcnn_delta_call.cpp srcnn_rgb_delta_call.cpp srcnn_capi.cpp srcnn_frames.cpp srcnn_pipeline.cpp srcnn_comm.cpp dropin.cpp
 endif
 OBJS    := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(basename $(SRCS))))
-HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_window.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_rect_source.hpp $(CSRC)/srcnn_y_path_geom.hpp $(CSRC)/srcnn_rect_atlas.hpp $(CSRC)/srcnn_rgb_rect_atlas.hpp $(CSRC)/srcnn_yuv_rect_atlas.hpp $(CSRC)/srcnn_yuv_packed_rect_atlas.hpp $(CSRC)/srcnn_yuv_chroma_tile.h $(CSRC)/srcnn_yuv_packed_merge_tile.h $(CSRC)/srcnn_rect_list.h $(CSRC)/srcnn_rect_list_call.hpp $(CSRC)/srcnn_delta.h $(CSRC)/srcnn_delta.hpp $(CSRC)/srcnn_rgb_delta.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_colour_rules.h $(CSRC)/srcnn_window_tile.h $(CSRC)/srcnn_yuv_packed_fields.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/srcnn_amd_rect.h include/srcnn_amd_rect_list.h include/srcnn_amd_rgb_rect.h include/srcnn_amd_rgb_rect_list.h include/srcnn_amd_yuv_rect.h include/srcnn_amd_yuv_rect_list.h include/srcnn_amd_yuv_packed_rect.h include/srcnn_amd_yuv_packed_rect_list.h include/srcnn_amd_delta.h include/srcnn_amd_rgb_delta.h include/libsrcnn_dropin.h
+HDRS    := $(CSRC)/srcnn_kernels.h $(CSRC)/srcnn_yuv.h $(CSRC)/srcnn_rgb.h $(CSRC)/srcnn_window.h $(CSRC)/srcnn_frame_rules.h $(CSRC)/srcnn_frame_args.hpp $(CSRC)/srcnn_rect_source.hpp $(CSRC)/srcnn_y_path_geom.hpp $(CSRC)/srcnn_rect_atlas.hpp $(CSRC)/srcnn_rgb_rect_atlas.hpp $(CSRC)/srcnn_yuv_rect_atlas.hpp $(CSRC)/srcnn_yuv_packed_rect_atlas.hpp $(CSRC)/srcnn_yuv_chroma_tile.h $(CSRC)/srcnn_yuv_packed_merge_tile.h $(CSRC)/srcnn_rect_list.h $(CSRC)/srcnn_rect_list_call.hpp $(CSRC)/srcnn_delta.h $(CSRC)/srcnn_delta.hpp $(CSRC)/srcnn_delta_call.hpp $(CSRC)/srcnn_rgb_delta.hpp $(CSRC)/srcnn_pixel_io.h $(CSRC)/srcnn_colour_rules.h $(CSRC)/srcnn_window_tile.h $(CSRC)/srcnn_yuv_packed_fields.h $(CSRC)/srcnn_host.hpp $(CSRC)/srcnn_owned.hpp $(CSRC)/srcnn_settings.hpp $(CSRC)/srcnn_watchdog.hpp $(CSRC)/resample_table.hpp $(CSRC)/srcnn_weights.inc include/srcnn_amd.h include/srcnn_amd_debug.h include/srcnn_amd_yuv.h include/srcnn_amd_yuv_ex.h include/srcnn_amd_yuv_packed.h include/srcnn_amd_rgb.h include/srcnn_amd_rect.h include/srcnn_amd_rect_list.h include/srcnn_amd_rgb_rect.h include/srcnn_amd_rgb_rect_list.h include/srcnn_amd_yuv_rect.h include/srcnn_amd_yuv_rect_list.h include/srcnn_amd_yuv_packed_rect.h include/srcnn_amd_yuv_packed_rect_list.h include/srcnn_amd_delta.h include/srcnn_amd_rgb_delta.h include/libsrcnn_dropin.h
 
 PREFIX  ?= /usr/local
 ROCM    ?= /opt/rocm

@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsrcnn_amd.so")
 
 SOURCES = ["srcnn_kernels.hip", "srcnn_fused_f16.hip", "srcnn_yuv_planes.hip", "srcnn_yuv_packed.hip", "srcnn_rgb.hip", "srcnn_rgb_window.hip", "srcnn_yuv_window.hip", "srcnn_yuv_packed_window.hip", "srcnn_window.hip", "srcnn_rect_list.hip", "srcnn_rgb_rect_list.hip", "srcnn_yuv_rect_list.hip", "srcnn_yuv_packed_rect_list.hip", "srcnn_delta.hip", "srcnn_rect_list_call.cpp", "srcnn_rgb_rect_list_call.cpp", "srcnn_yuv_rect_list_call.cpp", "srcnn_yuv_packed_rect_list_call.cpp", "srcnn_delta_call.cpp", "srcnn_rgb_delta_call.cpp", "srcnn_capi.cpp", "srcnn_frames.cpp", "srcnn_pipeline.cpp", "srcnn_comm.cpp", "dropin.cpp"]
-DEPS = SOURCES + ["../../tools/srcnntest.cpp", "../../tools/srcnnyuv.cpp", "srcnn_kernels.h", "srcnn_yuv.h", "srcnn_rgb.h", "srcnn_window.h", "srcnn_frame_rules.h", "srcnn_frame_args.hpp", "srcnn_rect_source.hpp", "srcnn_y_path_geom.hpp", "srcnn_rect_atlas.hpp", "srcnn_rgb_rect_atlas.hpp", "srcnn_yuv_rect_atlas.hpp", "srcnn_yuv_packed_rect_atlas.hpp", "srcnn_yuv_chroma_tile.h", "srcnn_yuv_packed_merge_tile.h", "srcnn_rect_list.h", "srcnn_rect_list_call.hpp", "srcnn_delta.h", "srcnn_delta.hpp", "srcnn_rgb_delta.hpp", "srcnn_pixel_io.h", "srcnn_colour_rules.h", "srcnn_window_tile.h", "srcnn_yuv_packed_fields.h", "srcnn_host.hpp", "srcnn_owned.hpp", "srcnn_settings.hpp", "srcnn_watchdog.hpp", "resample_table.hpp", "srcnn_weights.inc",
+DEPS = SOURCES + ["../../tools/srcnntest.cpp", "../../tools/srcnnyuv.cpp", "srcnn_kernels.h", "srcnn_yuv.h", "srcnn_rgb.h", "srcnn_window.h", "srcnn_frame_rules.h", "srcnn_frame_args.hpp", "srcnn_rect_source.hpp", "srcnn_y_path_geom.hpp", "srcnn_rect_atlas.hpp", "srcnn_rgb_rect_atlas.hpp", "srcnn_yuv_rect_atlas.hpp", "srcnn_yuv_packed_rect_atlas.hpp", "srcnn_yuv_chroma_tile.h", "srcnn_yuv_packed_merge_tile.h", "srcnn_rect_list.h", "srcnn_rect_list_call.hpp", "srcnn_delta.h", "srcnn_delta.hpp", "srcnn_delta_call.hpp", "srcnn_rgb_delta.hpp", "srcnn_pixel_io.h", "srcnn_colour_rules.h", "srcnn_window_tile.h", "srcnn_yuv_packed_fields.h", "srcnn_host.hpp", "srcnn_owned.hpp", "srcnn_settings.hpp", "srcnn_watchdog.hpp", "resample_table.hpp", "srcnn_weights.inc",
                   "../../include/srcnn_amd.h", "../../include/srcnn_amd_debug.h", "../../include/srcnn_amd_yuv.h", "../../include/srcnn_amd_yuv_ex.h", "../../include/srcnn_amd_yuv_packed.h", "../../include/srcnn_amd_rgb.h", "../../include/srcnn_amd_rect.h", "../../include/srcnn_amd_rect_list.h", "../../include/srcnn_amd_rgb_rect.h", "../../include/srcnn_amd_rgb_rect_list.h", "../../include/srcnn_amd_yuv_rect.h", "../../include/srcnn_amd_yuv_rect_list.h", "../../include/srcnn_amd_yuv_packed_rect.h", "../../include/srcnn_amd_yuv_packed_rect_list.h", "../../include/srcnn_amd_delta.h", "../../include/srcnn_amd_rgb_delta.h",
                   "../../include/libsrcnn_dropin.h", "exports.map"]
 

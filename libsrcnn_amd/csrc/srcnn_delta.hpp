@@ -1,6 +1,6 @@
 // srcnn_delta.hpp -- the host half of the delta call (include/srcnn_amd_delta.h) that needs no device: the tile grid, the two
-// span tables that say which source samples a tile depends on, the coalescer that turns the dirty flags into rects, and the
-// whole-frame rule.  It needs the contribution-table builder (resample_table.hpp) and the rect geometry (srcnn_rect_source.hpp)
+// span tables that say which source samples a tile depends on, the coalescer that turns the dirty flags into rects, the
+// whole-frame rule and the plan of a whole operation (delta_plan).  It needs the contribution-table builder (resample_table.hpp) and the rect geometry (srcnn_rect_source.hpp)
 // only -- no HIP -- so tests/host/delta_sanitize.cpp runs it under the CPU sanitizers.  Internal.
 //
 // The contract.  An output tile grid of tile_w x tile_h output samples covers dw x dh: cols = ceil(dw / tile_w), rows =
@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/srcnn_amd_rect_list.h"
+#include "../../include/srcnn_amd_delta.h"
 #include "resample_table.hpp"
 #include "srcnn_rect_source.hpp"
 
@@ -48,6 +48,17 @@ inline int delta_grid(unsigned w, unsigned h, unsigned dw, unsigned dh, int filt
     g.rows = (dh + g.tile_h - 1) / g.tile_h;
     if (g.cols > kDeltaMaxAxisTiles || g.rows > kDeltaMaxAxisTiles)
         return fail(SRCNN_E_UNSUPPORTED, "a grid of %u x %u tiles of %ux%u: at most %u a side", g.cols, g.rows, g.tile_w, g.tile_h, kDeltaMaxAxisTiles);
+    return SRCNN_OK;
+}
+
+// What the *_rects entry points of both delta calls refuse about a grid the caller states: tile sides given, not 0
+inline int check_delta_tiles(unsigned cols, unsigned rows, unsigned tile_w, unsigned tile_h, unsigned dw, unsigned dh)
+{
+    if (dw == 0 || dh == 0) return fail(SRCNN_E_SCALE, "scaled size %ux%u", dw, dh);
+    if (tile_w < kDeltaTileMin || tile_w > kDeltaTileMax || tile_h < kDeltaTileMin || tile_h > kDeltaTileMax)
+        return fail(SRCNN_E_ARG, "tile %ux%u: a side is %u ... %u", tile_w, tile_h, kDeltaTileMin, kDeltaTileMax);
+    if (cols != (dw + tile_w - 1) / tile_w || rows != (dh + tile_h - 1) / tile_h)
+        return fail(SRCNN_E_ARG, "%u x %u tiles of %ux%u do not cover %ux%u", cols, rows, tile_w, tile_h, dw, dh);
     return SRCNN_OK;
 }
 
@@ -161,6 +172,34 @@ inline bool delta_whole_frame(size_t rects, unsigned long long dirty_tiles, unsi
     if (dirty_tiles == tiles) return true;
     if (rects > kDeltaListMax) return true;
     return cell_samples * 1000ull >= (unsigned long long)permille * ((unsigned long long)dw * dh);
+}
+
+// ---- the plan of a whole operation ---------------------------------------------------------------------------------------------
+inline unsigned delta_rect_count(size_t n) { return (unsigned)std::min<size_t>(n, 0xffffffffu); }      // srcnn_delta_stats::rects
+
+// From the grid's flags on the host to what is repainted and what the caller is told.  host_flags == NULL: no previous frame --
+// every tile counts as dirty and the frame is the one rect.  Otherwise the dirty count and the coalescer, then the whole-frame
+// rule, which collapses `rects` to (0, 0, dw, dh); st.rects and st.cell_samples keep what the coalescer gave.  Empty `rects`:
+// nothing changed, nothing to repaint.
+inline void delta_plan(const unsigned char* host_flags, const DeltaGrid& g, unsigned dw, unsigned dh, long permille, srcnn_delta_stats& st,
+                       std::vector<DeltaRect>& rects)
+{
+    st = srcnn_delta_stats{};
+    st.struct_size = (unsigned)sizeof(srcnn_delta_stats);
+    st.tiles = g.cols * g.rows;
+    if (!host_flags) {
+        st.dirty_tiles = st.tiles;
+        rects.assign(1, DeltaRect{0, 0, dw, dh});
+    } else {
+        for (size_t k = 0; k < st.tiles; ++k) st.dirty_tiles += host_flags[k] != 0;
+        delta_coalesce(host_flags, g.cols, g.rows, g.tile_w, g.tile_h, dw, dh, rects);
+    }
+    st.rects = delta_rect_count(rects.size());
+    st.cell_samples = delta_cell_samples(rects);
+    if (delta_whole_frame(rects.size(), st.dirty_tiles, st.tiles, st.cell_samples, dw, dh, permille)) {
+        st.whole_frame = 1;
+        rects.assign(1, DeltaRect{0, 0, dw, dh});
+    }
 }
 
 }  // namespace srcnn

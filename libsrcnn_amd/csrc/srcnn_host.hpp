@@ -102,12 +102,17 @@ struct Scratch {            // the buffers of a Workspace: movable, so that a wo
     }
 };
 // What the delta call keeps beside Scratch::delta_spans / delta_flags.  The span tables depend on the geometry alone, so they
-// are uploaded when `key` changes and not again (a stream of frames: once).  `pin` receives the flags of
-// srcnn_y_path_delta_f32_dev, which waits for them before it returns, under the workspace's mutex: one buffer is enough.
+// are uploaded when `key` or `owner` changes and not again (a stream of frames: once).  `pin` receives the flags of a whole
+// delta operation, which waits for them before it returns, under the workspace's mutex: one buffer is enough.
+// owner: the delta calls share these buffers and build their tables by different rules (srcnn_delta.hpp, srcnn_rgb_delta.hpp),
+// so one call's tables must not answer for the other's.  Defensive: at every geometry compared so far the two rules gave the
+// same tables, so no test can tell a confused owner; nothing promises that they always will.
+enum class DeltaSpanOwner { YPlane, Rgb };
 struct DeltaStage {
     PinnedBuf pin;
     bool valid = false;
-    unsigned key[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // w, h, dw, dh, filter, tile_w, tile_h, whose: 0 = the Y call's tables, 1 = the RGB(A) call's
+    DeltaSpanOwner owner = DeltaSpanOwner::YPlane;
+    unsigned key[7] = {0, 0, 0, 0, 0, 0, 0};         // w, h, dw, dh, filter, tile_w, tile_h
 };
 // Page-locked staging of the rect list call's descriptor tables.  A call fills the next slot of the ring on the host, queues the
 // copy to Scratch::list on its stream and records the slot's event behind it; a slot is written again only after that event has

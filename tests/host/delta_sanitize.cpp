@@ -2,7 +2,8 @@
 // HIP.  Built and run by tests/test_delta_sanitizer.py with -fsanitize=address,undefined, the way
 // tests/test_yuv_rect_list_sanitizer.py builds its program.  What runs under the sanitizers is libsrcnn_amd/csrc/srcnn_delta.hpp:
 // the grid (delta_grid), the span-table builder (delta_axis_spans, delta_spans_monotone, delta_span_image), the coalescer
-// (delta_coalesce, delta_items) and the whole-frame rule (delta_whole_frame).  It asserts that
+// (delta_coalesce, delta_items), the whole-frame rule (delta_whole_frame), what the *_rects entry points refuse about a stated grid
+// (check_delta_tiles) and the plan of a whole operation (delta_plan).  It asserts that
 //   * the span of every tile column and row, built from ONE table per axis, is the rectangle y_path_rect_source_span gives for
 //     that tile on its own, for all five filters over the grids of the issue, a 2.5x frame, an axis that keeps its size and a
 //     down-scale, and that both ends are monotone -- what the kernel's bisection rests on;
@@ -11,7 +12,11 @@
 //     continues the open rect of the previous row only when its columns are identical), on seeded grids, on the hand cases and on
 //     degenerate grids (1 x 1, a 1-tile column, a 1-tile row);
 //   * delta_items writes nothing when the capacity is one short, and exactly n items otherwise;
-//   * every clause of the whole-frame rule.
+//   * every clause of the whole-frame rule;
+//   * check_delta_tiles refuses in its order -- scaled size, tile side, cover -- and accepts cols and rows at exactly the ceiling;
+//   * delta_plan yields, branch by branch, the rects and the srcnn_delta_stats of the whole operation: nothing dirty, one change
+//     (the two points tests/test_gpu_delta.py::test_canary_repaint pins on the device), every tile dirty, no previous frame, the
+//     cells at the threshold and one below it; the rect count is clamped to 32 bits.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -23,13 +28,13 @@
 using namespace srcnn;
 
 // The product's fail() lives in srcnn_capi.cpp; this one formats as well, so the sanitizers see every message's arguments.
+static char g_last[512];      // the last message
 namespace srcnn {
 int fail(int code, const char* fmt, ...)
 {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    vsnprintf(g_last, sizeof g_last, fmt, ap);
     va_end(ap);
     return code;
 }
@@ -173,6 +178,28 @@ static std::vector<unsigned char> grid_of(unsigned cols, unsigned rows, const ch
     return f;
 }
 
+// check_delta_tiles refuses with `code` and a message that holds `what`
+static bool refuses(int rc, int code, const char* what) { return rc == code && std::strstr(g_last, what); }
+
+// the plan of the 6 x 7 grid of 32 x 16 tiles over 192 x 112 (text: grid_of's, NULL: no previous frame)
+static srcnn_delta_stats plan_of(const char* text, long permille, std::vector<DeltaRect>& rects)
+{
+    const DeltaGrid g{32, 16, 6, 7};
+    std::vector<unsigned char> f;
+    if (text) f = grid_of(6, 7, text);
+    srcnn_delta_stats st;
+    std::memset(&st, 0xEE, sizeof st);
+    rects.assign(3, DeltaRect{9, 9, 9, 9});              // (what the call's vector held before does not matter)
+    delta_plan(text ? f.data() : nullptr, g, 192, 112, permille, st, rects);
+    CHECK(st.struct_size == sizeof(srcnn_delta_stats), "struct_size %u", st.struct_size);
+    return st;
+}
+static bool stats_are(const srcnn_delta_stats& s, unsigned tiles, unsigned dirty, unsigned rects, unsigned whole, unsigned long long cells)
+{
+    return s.tiles == tiles && s.dirty_tiles == dirty && s.rects == rects && s.whole_frame == whole && s.cell_samples == cells;
+}
+static bool is_rect(const DeltaRect& r, unsigned x0, unsigned y0, unsigned rw, unsigned rh) { return r.x0 == x0 && r.y0 == y0 && r.rw == rw && r.rh == rh; }
+
 int main()
 {
     // ---- span tables ----
@@ -236,6 +263,34 @@ int main()
     CHECK(!delta_whole_frame(65536, 65536, 1u << 20, 65536ull * 400, 7680, 8192, 1000), "65536 rects are a list");
     std::vector<DeltaRect> two = {{64, 32, 64, 48}, {0, 0, 64, 32}};
     CHECK(delta_cell_samples(two) == 4560 + 3344, "cell samples");
+
+    // ---- a stated grid: each refusal in order, then the accepted edges ----
+    CHECK(refuses(check_delta_tiles(9, 9, 7, 7, 0, 112), SRCNN_E_SCALE, "scaled size") && refuses(check_delta_tiles(9, 9, 7, 7, 192, 0), SRCNN_E_SCALE, "scaled size"), "the size first");
+    CHECK(refuses(check_delta_tiles(9, 9, 7, 16, 192, 112), SRCNN_E_ARG, "a side is") && refuses(check_delta_tiles(9, 9, 32, 65536, 192, 112), SRCNN_E_ARG, "a side is") &&
+          refuses(check_delta_tiles(9, 9, 0, 16, 192, 112), SRCNN_E_ARG, "a side is"), "then the tile, 0 included: no default here");
+    CHECK(refuses(check_delta_tiles(5, 7, 32, 16, 192, 112), SRCNN_E_ARG, "do not cover") && refuses(check_delta_tiles(7, 7, 32, 16, 192, 112), SRCNN_E_ARG, "do not cover") &&
+          refuses(check_delta_tiles(6, 6, 32, 16, 192, 112), SRCNN_E_ARG, "do not cover") && refuses(check_delta_tiles(6, 8, 32, 16, 192, 112), SRCNN_E_ARG, "do not cover"), "then the cover");
+    CHECK(check_delta_tiles(6, 7, 32, 16, 192, 112) == SRCNN_OK && check_delta_tiles(5, 5, 40, 24, 192, 112) == SRCNN_OK, "cols and rows at the ceiling, whole and partial last tiles");
+    CHECK(check_delta_tiles(24, 14, 8, 8, 192, 112) == SRCNN_OK && check_delta_tiles(1, 1, 65535, 65535, 192, 112) == SRCNN_OK, "the smallest and the largest tile");
+
+    // ---- the plan of a whole operation, branch by branch (850: the default of SRCNN_DELTA_WHOLE_PERMILLE) ----
+    std::vector<DeltaRect> rects;
+    CHECK(stats_are(plan_of("...... ...... ...... ...... ...... ...... ......", 850, rects), 42, 0, 0, 0, 0) && rects.empty(), "nothing dirty: no rects, not the whole frame");
+    // the two points of tests/test_gpu_delta.py::test_canary_repaint, from the flags its restatement expects
+    CHECK(stats_are(plan_of("...... ...... ..##.. ..##.. ..##.. ...... ......", 850, rects), 42, 6, 1, 0, 4560) && rects.size() == 1 && is_rect(rects[0], 64, 32, 64, 48), "a change at (48, 28)");
+    CHECK(stats_are(plan_of("##.... ##.... ...... ...... ...... ...... ......", 850, rects), 42, 4, 1, 0, 3344) && rects.size() == 1 && is_rect(rects[0], 0, 0, 64, 32), "a change at (20, 10)");
+    CHECK(stats_are(plan_of("...... ...... ...... ..#... ...... ...... ......", 850, rects), 42, 1, 1, 0, 44 * 28) && rects.size() == 1 && is_rect(rects[0], 64, 48, 32, 16), "one tile");
+    CHECK(stats_are(plan_of("###### ###### ###### ###### ###### ###### ######", 1000000, rects), 42, 42, 1, 1, 204 * 124) && rects.size() == 1 && is_rect(rects[0], 0, 0, 192, 112),
+          "every tile dirty, whatever the switch");
+    CHECK(stats_are(plan_of(nullptr, 1000000, rects), 42, 42, 1, 1, 204 * 124) && rects.size() == 1 && is_rect(rects[0], 0, 0, 192, 112), "no previous frame: as if every tile were dirty");
+    // 4560 / 21504 = 0.21205: reached at 212, not at 213; the rects collapse to the one, the stats keep what the coalescer gave
+    CHECK(stats_are(plan_of("...... ...... ..##.. ..##.. ..##.. ...... ......", 212, rects), 42, 6, 1, 1, 4560) && rects.size() == 1 && is_rect(rects[0], 0, 0, 192, 112), "at the threshold");
+    CHECK(stats_are(plan_of("...... ...... ..##.. ..##.. ..##.. ...... ......", 213, rects), 42, 6, 1, 0, 4560) && rects.size() == 1 && is_rect(rects[0], 64, 32, 64, 48), "one below it");
+    CHECK(stats_are(plan_of("##.... ##.... ..##.. ..##.. ..##.. ...... ......", 367, rects), 42, 10, 2, 1, 7904) && rects.size() == 1 && is_rect(rects[0], 0, 0, 192, 112), "7904 / 21504 = 0.36756, two rects");
+    CHECK(stats_are(plan_of("##.... ##.... ..##.. ..##.. ..##.. ...... ......", 368, rects), 42, 10, 2, 0, 7904) && rects.size() == 2 && is_rect(rects[0], 0, 0, 64, 32) && is_rect(rects[1], 64, 32, 64, 48),
+          "two rects, in the order they were opened");
+    CHECK(delta_rect_count(0) == 0 && delta_rect_count(65537) == 65537 && delta_rect_count((size_t)0xffffffffu) == 0xffffffffu &&
+          delta_rect_count((size_t)0xffffffffu + 1) == 0xffffffffu && delta_rect_count((size_t)1 << 40) == 0xffffffffu, "the rect count is clamped to 32 bits");
 
     if (g_fail) { std::printf("%d checks FAILED\n", g_fail); return 1; }
     std::printf("all checks passed\n");

@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import rgb_delta_worker as DWK  # noqa: E402
+import test_gpu_delta as YD  # noqa: E402
 from rect_list_worker import DH, DW, H, W  # noqa: E402
 from rgb_rect_list_worker import arrange, canonical  # noqa: E402
 from test_gpu_rgb import first_difference  # noqa: E402
@@ -361,6 +362,44 @@ def test_other_geometry(srcnn, w, h, mul, filt, tile):
         got = rig.check(rig.changed([(x, y, rig.nplanes - 1, rig.bpp - 1)]), "%r" % ((x, y),))
         assert np.array_equal(got, rig.geo.of_pixel(x, y))
     assert rig.check((rig.prev ^ 0x01).astype(rig.prev.dtype), "every sample").all()
+
+
+# ---- the span tables both delta calls keep in one place ----
+def test_y_and_rgb_flags_back_to_back_on_one_stream(srcnn):
+    """srcnn_y_path_delta_flags_dev, srcnn_rgb_delta_flags_dev and srcnn_y_path_delta_flags_dev again, queued on one stream with
+    nothing between them, each into a flag buffer of its own and each compared with its restatement.  The two calls keep their
+    span tables in the same buffer of the stream's workspace, so each call here invalidates the tables of the one before and
+    uploads its own while that one's kernel may still be reading: first with the RGB(A) image at the Y plane's geometry, then at
+    another.  This guards the order of invalidate, upload and launch.  It cannot tell whose tables a call used: for these
+    geometries both rules give the same tables."""
+    S = srcnn
+    bicubic = S.SRCNNF_Bicubic
+    ygeo = YD.Geo(S, filt=bicubic, tile=(16, 16))
+    plane = YD.RW.frame_plane()
+    ycurs = [YD.changed(plane, [(5, 3), (70, 40)]), YD.changed(plane, [(90, 55), (33, 20)])]
+    ywants = [ygeo.expected(plane, c) for c in ycurs]
+    assert ywants[0].any() and not np.array_equal(ywants[0], ywants[1])
+    for kw in (dict(tile=(16, 16)), dict(w=40, h=31, mul=1.5, tile=(16, 8))):
+        rig = Rig(S, filt=bicubic, **kw)
+        rgeo = rig.geo
+        rcur = rig.changed([(7, 9, 0, 1), (rgeo.w - 1, rgeo.h - 1, 0, 0)])
+        wants = [ywants[0], rgeo.expected(rig.prev, rcur, rig.layout), ywants[1]]
+        assert wants[1].any() and not wants[1].all()
+        dplane = YD.upload(S, plane, fill=1)[0]
+        dycurs = [YD.upload(S, c, fill=2 + k)[0] for k, c in enumerate(ycurs)]
+        dprev = upload(S, rig.prev, rig.layout, fill=1)[0]
+        dcur = upload(S, rcur, rig.layout, fill=2)[0]
+        fbufs = [S.DeviceBuffer.from_numpy(np.full(want.size + 2 * GUARD, CANARY, np.uint8)) for want in wants]
+        S.sync()
+        S.y_path_delta_flags_dev(dplane, 0, dycurs[0], 0, ygeo.w, ygeo.h, ygeo.dw, ygeo.dh, bicubic, ygeo.tile, (fbufs[0], GUARD))
+        S.rgb_delta_flags_dev(rig.fmt, rgeo.w, rgeo.h, rgeo.mul, bicubic, dprev, None, dcur, None, rgeo.tile, (fbufs[1], GUARD))
+        S.y_path_delta_flags_dev(dplane, 0, dycurs[1], 0, ygeo.w, ygeo.h, ygeo.dw, ygeo.dh, bicubic, ygeo.tile, (fbufs[2], GUARD))
+        S.sync()
+        for k, (fbuf, want) in enumerate(zip(fbufs, wants)):
+            raw = fbuf.to_numpy(np.uint8, (want.size + 2 * GUARD,))
+            assert np.all(raw[:GUARD] == CANARY) and np.all(raw[GUARD + want.size:] == CANARY), "call %d wrote a guard byte of its flag buffer" % k
+            got = raw[GUARD:GUARD + want.size].reshape(want.shape)
+            assert np.array_equal(got, want), "call %d of the sequence, RGB(A) at %r\ngot\n%s\nwant\n%s" % (k, kw, got, want)
 
 
 # ---- end to end, strict ----
