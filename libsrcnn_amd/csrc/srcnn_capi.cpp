@@ -1740,12 +1740,15 @@ int srcnn_conv12_f32_dev(const float* d_y, unsigned w, unsigned h, float* d_c2, 
     int rc;
     if ((rc = check_plane(d_y, w, h, d_c2))) return rc;
     if (h > 65535u * 4u) return fail(SRCNN_E_UNSUPPORTED, "too many rows");
-    Call c;
-    c.cx = ctx_for_stream(stream);
-    if (!c.cx) return SRCNN_E_NODEVICE;
-    c.s = (hipStream_t)stream; c.mode = G.mode.load();
-    run_conv12(c, d_y, (int)w, (int)h, 0, (int)h, d_c2, (size_t)w * h, 0, (int)h);
-    HIP_TRY(hipGetLastError());
+    // On the stream's own workspace, like every path: run_conv12 draws tiles from the workspace's queue, and a call without a
+    // workspace would deal them with the static stride -- not the form the hot path runs (tests/test_gpu_conv12_tile_loop.py).
+    StreamCall sc(stream);
+    if (sc.rc) return sc.rc;
+    run_conv12(sc.c, d_y, (int)w, (int)h, 0, (int)h, d_c2, (size_t)w * h, 0, (int)h);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+        sc.c.ws->queue_dirty = true;                   // re-zeroed on the launch stream before the next launch trusts it
+        return fail(SRCNN_E_HIP, "srcnn_conv12_f32_dev: %s", hipGetErrorString(e));
+    }
     return SRCNN_OK;
 }
 

@@ -308,7 +308,8 @@ def test_host_stream_equals_singles(srcnn, use_graph):
                          ids=["no-dma-staging", "static-stride", "no-spread-64bit-offsets"])
 def test_fallback_layer_kernels_bit_exact(env, golden, tmp_path):
     """The one fallback each layer kernel keeps (round 5: production + one fallback per kernel; the switches are read when
-    the library is loaded, hence a subprocess) reproduces the golden output bit for bit."""
+    the library is loaded, hence a subprocess) reproduces the golden output bit for bit.  These planes are small enough that every
+    workgroup of the layer-1+2 kernel runs one item; the looping forms of its fallbacks are in tests/test_gpu_conv12_tile_loop.py."""
     import os
     import subprocess
     import sys
