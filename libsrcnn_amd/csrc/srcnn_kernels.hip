@@ -675,6 +675,13 @@ constexpr int m_lds_floats(bool ld) { return M_W1 + M_W2 + M_B1 + M_B2 + m_ybufs
 // RELAX: bit 0 = layer 1, bit 1 = layer 2 evaluated as FMA chains on the matrix pipe (C = acc: one rounding per tap instead of
 // the reference's two).  0 = STRICT (production, bit-exact), 3 = SRCNN_MODE_FAST; 1 and 2 exist for the per-layer error
 // matrix (profiles/r04_error_matrix.txt) and the SRCNN_MODE_RELAXED experiments.
+//   The relaxed forms are a contract too, checked bit for bit against oracle/srcnn_tiers.c (tests/test_gpu_tiers_exact.py):
+//   layer 1  acc = fmaf(w1[k][t], y[t], acc) over the 81 taps from 0 (v_mfma_f32_32x32x1, C = acc), then + b1[k] and ReLU;
+//   layer 2  (the FAST branch below) 32 v_mfma_f32_32x32x2f32 steps with C = acc2 over the channel pairs (2p, 2p+1).  Inside one
+//            K=2 step gfx950 takes the pair IN ORDER with one rounding per channel: acc2 = fmaf(w[2p+1], x[2p+1],
+//            fmaf(w[2p], x[2p], acc2)) -- a plain 64-term fmaf chain over channels 0..63 -- then + b2[m] and ReLU.  Measured on
+//            the device, not documented: the reversed pair and the once-rounded sum acc2 + w0 x0 + w1 x1 give other bits on
+//            23 % and 36 % of the samples.
 // TIERS: strict layer 2 chooses per 32-channel block and 32-pixel segment between the full body and one body per tier of
 // MT_TIER (production: <0, true, true>, SRCNN_CONV12_TIERS, profiles/conv12_tiers_ab.txt).  TIERS = false chooses between
 // the full body and the body without M_DEAD's members, and only where `prune` is set (SRCNN_CONV12_PRUNE); the TIERS instance

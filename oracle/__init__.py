@@ -5,6 +5,8 @@ Import from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg, now
 `Reference()` binds oracle/_ref/libsrcnn_ref.so (the real reference compiled from
 /root/reference/src by oracle/Makefile, present only if it was built in the dev container and
 travelled with the snapshot).  Both expose the same stage-level calls on numpy arrays.
+`Tiers()` binds oracle/_build/libsrcnn_tiers.so (srcnn_tiers.c): the product's own stated arithmetic
+for its fp32 non-parity tiers, restated so that they too are checked at tolerance 0.
 """
 import ctypes as C
 import os
@@ -14,6 +16,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(_HERE, "_build", "libsrcnn_oracle.so")
+TIERS_SO = os.path.join(_HERE, "_build", "libsrcnn_tiers.so")
 REF_SO = os.path.join(_HERE, "_ref", "libsrcnn_ref.so")
 REF_SRC = "/root/reference/src"
 
@@ -226,3 +229,63 @@ class Reference(_Stages):
             raise RuntimeError("ProcessSRCNN rc=%d" % rc)
         assert osz.value == out.size and csz.value == conv.size, (osz.value, csz.value)
         return out, conv
+
+
+class Tiers:
+    """The fp32 non-parity tiers (SRCNN_RELAX_* bits, SRCNN_MODE_FAST) as the product states them, on the layouts of
+    Oracle.conv1 / conv2 / conv3.  With nothing relaxed every call is Oracle's, bit for bit."""
+    K2_STRICT, K2_A, K2_B, K2_C = range(4)          # layer 2: the reference, or one model of the K=2 MFMA step
+    K2_NAMES = {K2_A: "A: fmaf(w1, x1, fmaf(w0, x0, acc))", K2_B: "B: fmaf(w0, x0, fmaf(w1, x1, acc))",
+                K2_C: "C: acc + w0 x0 + w1 x1, rounded once"}
+    L3_STRICT, L3_X64, L3_F32 = range(3)            # layer 3: the reference, SRCNN_RELAX_L3_X64, SRCNN_RELAX_L3_F32
+
+    def __init__(self, oracle=None):
+        if not os.path.exists(TIERS_SO):
+            build(ref=False)
+        self.lib = C.CDLL(TIERS_SO)
+        self.oracle = oracle if oracle is not None else Oracle()
+        for n in ("conv1", "conv2", "conv3"):
+            f = getattr(self.lib, "tiers_" + n)
+            f.argtypes = [_f32p, C.c_uint, C.c_uint, C.c_int, _f32p]
+            f.restype = None
+        self.lib.tiers_layers.argtypes = [_f32p, C.c_uint, C.c_uint, C.c_uint, C.c_int, _f32p]
+        self.lib.tiers_layers.restype = C.c_int
+
+    def conv1(self, y, fma=False):
+        y = np.ascontiguousarray(y, np.float32)
+        h, w = y.shape
+        out = np.empty((64, h, w), np.float32)
+        set_team(w * h)
+        self.lib.tiers_conv1(y, w, h, int(bool(fma)), out)
+        return out
+
+    def conv2(self, c1, model=K2_STRICT):
+        c1 = np.ascontiguousarray(c1, np.float32)
+        _, h, w = c1.shape
+        out = np.empty((32, h, w), np.float32)
+        set_team(w * h)
+        self.lib.tiers_conv2(c1, w, h, int(model), out)
+        return out
+
+    def conv3(self, c2, kind=L3_STRICT):
+        c2 = np.ascontiguousarray(c2, np.float32)
+        _, h, w = c2.shape
+        out = np.empty((h, w), np.float32)
+        set_team(w * h)
+        self.lib.tiers_conv3(c2, w, h, int(kind), out)
+        return out
+
+    def y_path(self, y, dw=None, dh=None, filt=FILTER_BICUBIC, mask=0, model=K2_A):
+        """The oracle's (strict) resample to (dw, dh) (default 2x), then the three layers under the SRCNN_RELAX_* bits of
+        `mask`, layer 2 under K=2 model `model` where bit 2 is set."""
+        y = np.ascontiguousarray(y, np.float32)
+        h, w = y.shape
+        dw = 2 * w if dw is None else dw
+        dh = 2 * h if dh is None else dh
+        up = self.oracle.resample(y, dw, dh, filt)
+        out = np.empty((dh, dw), np.float32)
+        set_team(dw * dh)
+        rc = self.lib.tiers_layers(up, dw, dh, int(mask), int(model), out)
+        if rc != 0:
+            raise ValueError("tiers_layers(mask=%d, model=%d) rc=%d" % (mask, model, rc))
+        return out

@@ -37,7 +37,7 @@ def planes(h, w):
     """[(name, plane)] for one shape.  `mix` puts a constant region, a smooth crop and a noise crop side by side with one
     seam on a segment boundary (column 32) and one inside a segment (column 45, and column 77 / 109 where the plane is that
     wide); rows change regions at h / 2, inside a 16-row tile."""
-    big = (max(h, 80), max(w, 160))
+    big = (max(h + 7, 80), max(w + 11, 160))        # room for the crops below (the shapes of this file: 80 x 160, as ever)
     smooth = synth.plane(big[0], big[1], SEED, "smooth")[7:7 + h, 11:11 + w].copy()
     noise = synth.plane(big[0], big[1], SEED + 1, "noise")[3:3 + h, 5:5 + w].copy()
     flat = np.full((h, w), FLAT, np.float32)
