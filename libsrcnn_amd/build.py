@@ -74,26 +74,21 @@ def kernel_source_sha(name="k_conv12_mfma"):
     """sha256 of everything that decides what one launch of a kernel moves through HBM: profiles that quote a counter for
     that kernel record it, and bench.py refuses to quote a counter taken from a different text.  Covered: the kernel's body
     (from its template header to the next banner comment) and, for the layer kernels, the constants its tile and LDS geometry
-    are built from (M_* / m_* and the zero tiers MT_* for k_conv12_mfma, C3_* for k_conv3), the LDS-DMA primitive rs_dma_dword they stage through, the
-    launchers that set grid, block and dynamic LDS (launch_conv12_mfma / conv12_grid_info, launch_conv3) and the
-    host function that picks the variant (run_conv12 in srcnn_capi.cpp).
-    Layer 3 has two fingerprints.  "k_conv3" is the template and launch_conv3, as ever.  "k_conv3_sparse" is what the strict
-    path runs by default: that kernel's section (its banner comment, C3_SPARSE, its body), the C3_* constants and rs_dma_dword
-    it shares with k_conv3, launch_layer3, which picks between the two, and launch_conv3, which launch_layer3 falls back to.
+    are built from (M_* / m_* and the zero tiers MT_* for k_conv12_mfma, C3_* with C3_SPARSE for k_conv3), the LDS-DMA
+    primitives they stage through (rs_dma_dword; rs_dma_dword_s for k_conv3's body columns), the launchers that set grid, block
+    and dynamic LDS and pick the instance (launch_conv12_mfma / conv12_grid_info, launch_conv3) and the host function that
+    picks the variant (run_conv12 in srcnn_capi.cpp).
+    Layer 3 has one: every instance of k_conv3, the one that skips all-zero channel windows and that the strict path runs by
+    default included, is the one template, launched by the one launcher.
     Layers 1+2 have one: every instance of k_conv12_mfma, the nested-tiers one that the strict path runs by default included,
     is the one template, launched by the one launcher, picked by run_conv12."""
     import hashlib
     import re
     src = open(os.path.join(CSRC, "srcnn_kernels.hip")).read()
     m = re.search(r"template <[^>]*>\s*__global__[^\n]*void %s\(" % re.escape(name), src)
-    banners = {"k_conv3_sparse": r"// =+\n// conv3, strict, skipping all-zero channel windows"}
-    if not m and name in banners:                     # not a template: from the banner that opens its section
-        m = re.search(banners[name], src)
-        if m and not re.search(r"__global__[^\n]*void %s\(" % name, src[m.end():src.find("// ====", src.find("__global__", m.end()))]):
-            m = None
     if not m:
         return None
-    end = src.find("// ====", src.find("__global__", m.end()) if name in banners else m.end())
+    end = src.find("// ====", m.end())
     parts = [src[m.start():end if end > 0 else len(src)]]
     extra = []
     if name == "k_conv12_mfma":
@@ -105,11 +100,7 @@ def kernel_source_sha(name="k_conv12_mfma"):
     elif name == "k_conv3":
         extra = [_region(src, r"constexpr int C3_TW\b", r"\ntemplate <bool STRICT"),
                  _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),
-                 _region(src, r"void launch_conv3\(", r"\n}\n")]
-    elif name == "k_conv3_sparse":
-        extra = [_region(src, r"constexpr int C3_TW\b", r"\ntemplate <bool STRICT"),
-                 _region(src, r"__device__ __forceinline__ void rs_dma_dword\(", r"\n}\n"),
-                 _region(src, r"void launch_layer3\(", r"\n}\n"),
+                 _region(src, r"__device__ __forceinline__ void rs_dma_dword_s\(", r"\n}\n"),
                  _region(src, r"void launch_conv3\(", r"\n}\n")]
     if any(e is None for e in extra):
         return None                      # a region moved: better no fingerprint than a partial one

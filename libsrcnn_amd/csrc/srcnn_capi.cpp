@@ -972,7 +972,7 @@ int y_path_pass(Call& c, const char* who, unsigned W, unsigned dh, unsigned r0, 
     }
     {
         StageTimer t(SRCNN_STAGE_CONV3, c);
-        launch_layer3(ws.c2.data(), plane, (int)W, (int)dh, (int)v.ca, (int)(v.cb - v.ca), d_out, (int)r0, (int)(r1 - r0), c.relax(), c.s);
+        launch_conv3(ws.c2.data(), plane, (int)W, (int)dh, (int)v.ca, (int)(v.cb - v.ca), d_out, (int)r0, (int)(r1 - r0), c.relax(), c.s);
     }
     store();
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
@@ -1730,7 +1730,7 @@ int srcnn_conv3_f32_dev(const float* d_c2, unsigned w, unsigned h, float* d_out,
     if (!ctx_for_stream(stream)) return SRCNN_E_NODEVICE;
     Call c;
     c.mode = G.mode.load();
-    launch_layer3(d_c2, (size_t)w * h, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, c.relax(), (hipStream_t)stream);
+    launch_conv3(d_c2, (size_t)w * h, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, c.relax(), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SRCNN_OK;
 }

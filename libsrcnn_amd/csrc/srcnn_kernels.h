@@ -120,12 +120,10 @@ void conv12_grid_info(int num_cus, int* blocks, int* tile_rows);
 // the same two numbers at compile time (srcnn_kernels.hip static_asserts them against M_TH / M_BPC): tile height and resident
 // workgroups per CU of the layer-1+2 kernel
 constexpr int kConv12TileRows = 16, kConv12BlocksPerCU = 2;
-// relax: RELAX_L3_X64 / RELAX_L3_F32 bits (neither = strict)
+// relax: RELAX_L3_X64 / RELAX_L3_F32 bits (neither = strict: the k_conv3 instance that skips all-zero channel windows,
+//        SRCNN_CONV3_SKIP, where it applies, else one without the test)
 void launch_conv3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out,
                   int out_row0, int out_rows, int relax, hipStream_t s);
-// what the callers use: k_conv3_sparse (strict, skips all-zero channel windows: SRCNN_CONV3_SKIP) where it applies, else launch_conv3
-void launch_layer3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out,
-                   int out_row0, int out_rows, int relax, hipStream_t s);
 void launch_conv1_planes(const float* Y, int W, int H, float* C1, hipStream_t s);
 void launch_conv2_planes(const float* C1, size_t n, float* C2v, hipStream_t s);
 void launch_rgb_split(const unsigned char* rgb, size_t n, int d, float* Yp, float* Cb, float* Cr, float* A,

@@ -1032,6 +1032,12 @@ static_assert(C3_LH % 4 == 0, "row slots");
 // channels per double-buffered LDS stage: 2 with DMA staging (25.6 KB of LDS and 76 VGPRs: six workgroups per CU), 4 with
 // register staging (47.4 KB: three)
 constexpr int c3_mc(bool sdma) { return sdma ? 2 : 4; }
+// C3_SPARSE: layer-2 channels (bit m = channel m) that are often all zero over everything a wave reads, its 68 x 8 window
+// (64 columns x 4 rows + 2 halo).  The SKIP instance tests these, and only these, and skips the channel's arithmetic for a wave
+// that has just SEEN the window all +-0, so ANY set is correct; it only has to be good.  tools/conv3_zero_windows.py counts
+// such windows per channel (profiles/conv3_zero_windows.txt: 26 on nearly every window of every input, 29 / 13 / 1 on
+// 78 / 47 / 30 % of the smooth generator's; no other channel reaches 25 % on any input).
+constexpr unsigned C3_SPARSE = 0x24002002u;       // 1 13 26 29
 
 // X64 (experiment, SRCNN_MODE_RELAXED bit 2): the products are formed exactly -- v_fma_f64 on widened operands -- instead of
 // being rounded to fp32 first; everything else (per-channel fp64 sum in window order, fp32 running sum over the channels,
@@ -1046,11 +1052,20 @@ constexpr int c3_mc(bool sdma) { return sdma ? 2 : 4; }
 // / v_add_f64 issue closer to their rate with six waves per SIMD: 2.24 vs 2.30 ms per 8K frame, the whole path -1 %.
 // 1-channel stages (32 barriers per tile) and 7-8 waves per SIMD (spills) are slower: 3.1 / 5.4 / 8.3 ms.
 // SDMA = false (SRCNN_CONV3_WDMA=0): the register-staged 4-channel form it replaced.
-template <bool STRICT, bool OFF64 = false, bool X64 = false, bool SDMA = false>
+// SKIP (SRCNN_CONV3_SKIP, default 1; the production layer-3 kernel is <true, false, false, true, true>): a wave skips a channel
+// of C3_SPARSE whose activations are all +-0 over its 68 x 8 window -- one test per candidate channel inside the channel loop;
+// tile, stages, DMA, waits, barriers and the arithmetic order are those of the SDMA instance, which SRCNN_CONV3_SKIP=0 runs
+// (profiles/conv3_skip_ab.txt; the fold of the two: profiles/conv3_fold_isa.txt).
+// Skipping changes no stored bit: every lane's 100 products are (+-0) x (a finite weight; tests/test_gpu_conv3_skip.py checks
+// the table) = +-0, so each fp64 accumulator a[q] is +-0, and (float)((double)sum + +-0) is sum for every nonzero or NaN sum.
+// sum itself starts at +0.0f and is only ever the rounded result of an fp64 add that began from +0, which round-to-nearest
+// never makes -0, so (+0) + (-0) = +0 is sum as well.  NaN or Inf in any other channel is not touched.
+template <bool STRICT, bool OFF64 = false, bool X64 = false, bool SDMA = false, bool SKIP = false>
 __global__ __launch_bounds__(256, SDMA ? 6 : 3) void k_conv3(
     const float* __restrict__ C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows,
     float* __restrict__ out, int out_row0, int out_rows, int weights_by_dma)
 {
+    static_assert(!SKIP || (STRICT && SDMA && !OFF64 && !X64), "the zero-window test belongs to the strict LDS-DMA instance");
     constexpr int C3_MC = c3_mc(SDMA);
     constexpr int C3_BODY = C3_MC * C3_LH / 4;         // body loads per thread per chunk (4 row slots)
     constexpr int C3_HALO = (C3_MC * C3_LH * 4 + 255) / 256;
@@ -1210,47 +1225,6 @@ __global__ __launch_bounds__(256, SDMA ? 6 : 3) void k_conv3(
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) sum[q] = (float)((double)sum[q] + a[q]);
-            } else if constexpr (STRICT && SDMA) {
-                // As the branch below, with the window rows addressed from two fixed bases and the fifth window column
-                // read as the (row k, row k+1) pairs its packed products consume -- pixels (q, q+1) share a weight there.
-                typedef float f2 __attribute__((ext_vector_type(2)));
-                const float* tA = cur + m * C3_CH + offA;
-                const float* tB = cur + m * C3_CH + offB;
-                f2 va[8], vb[8], vp[7];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    va[r] = f2{tA[r * C3_LW + 0], tA[r * C3_LW + 1]};
-                    vb[r] = f2{tA[r * C3_LW + 2], tA[r * C3_LW + 3]};
-                    va[r + 4] = f2{tB[r * C3_LW + 0], tB[r * C3_LW + 1]};
-                    vb[r + 4] = f2{tB[r * C3_LW + 2], tB[r * C3_LW + 3]};
-                }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    vp[k] = f2{tA[k * C3_LW + 4], tA[(k + 1) * C3_LW + 4]};
-                    vp[k + 4] = f2{tB[k * C3_LW + 4], tB[(k + 1) * C3_LW + 4]};
-                }
-                vp[3] = f2{tA[3 * C3_LW + 4], tB[4]};
-                const float* wrow = w3s + (c * C3_MC + m) * 30;
-                double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int dy = 0; dy < 5; ++dy) {
-                    const f2 wa = f2{wrow[dy * 6 + 0], wrow[dy * 6 + 1]};
-                    const f2 wb = f2{wrow[dy * 6 + 2], wrow[dy * 6 + 3]};
-                    const f2 wc = f2{wrow[dy * 6 + 4], wrow[dy * 6 + 4]};
-                    const f2 pc01 = wc * vp[dy], pc23 = wc * vp[dy + 2];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f2 pa = wa * va[q + dy], pb = wb * vb[q + dy];
-                        const float pc = q == 0 ? pc01.x : q == 1 ? pc01.y : q == 2 ? pc23.x : pc23.y;
-                        a[q] = (dy == 0) ? (double)pa.x : a[q] + (double)pa.x;
-                        a[q] = a[q] + (double)pa.y;
-                        a[q] = a[q] + (double)pb.x;
-                        a[q] = a[q] + (double)pb.y;
-                        a[q] = a[q] + (double)pc;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) sum[q] = (float)((double)sum[q] + a[q]);
             } else if constexpr (STRICT) {
                 // Products two at a time (v_pk_mul_f32) with BOTH operands already sitting in register pairs: the window
                 // row as (c0,c1) (c2,c3) c4 straight from ds_read2_b32, the channel's weights in the same shape from the
@@ -1260,14 +1234,48 @@ __global__ __launch_bounds__(256, SDMA ? 6 : 3) void k_conv3(
                 // v_pk_mul_f32 per channel at their measured issue rates (4.4 / 5.5 / 4.4 cycles, profiles/r01_valu_rates.txt:
                 // 1305 cycles per wave-channel predicted, 1298 measured); the movs rode in their shadow.  2-channel stages
                 // with 4 waves per SIMD: 2.48 ms (more barriers, spills).
+                // SDMA: the window rows are addressed from two fixed bases, and the fifth window column is read as the
+                // (row k, row k+1) pairs its packed products consume -- pixels (q, q+1) share a weight there.
                 typedef float f2 __attribute__((ext_vector_type(2)));
-                f2 va[8], vb[8];
-                float vc[8];
+                f2 va[8], vb[8], vp[7];         // vp: SDMA
+                float vc[8];                    // vc: the register-staged form
+                if constexpr (SDMA) {
+                    const float* tA = cur + m * C3_CH + offA;
+                    const float* tB = cur + m * C3_CH + offB;
 #pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    va[r] = f2{t[r * C3_LW + 0], t[r * C3_LW + 1]};
-                    vb[r] = f2{t[r * C3_LW + 2], t[r * C3_LW + 3]};
-                    vc[r] = t[r * C3_LW + 4];
+                    for (int r = 0; r < 4; ++r) {
+                        va[r] = f2{tA[r * C3_LW + 0], tA[r * C3_LW + 1]};
+                        vb[r] = f2{tA[r * C3_LW + 2], tA[r * C3_LW + 3]};
+                        va[r + 4] = f2{tB[r * C3_LW + 0], tB[r * C3_LW + 1]};
+                        vb[r + 4] = f2{tB[r * C3_LW + 2], tB[r * C3_LW + 3]};
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        vp[k] = f2{tA[k * C3_LW + 4], tA[(k + 1) * C3_LW + 4]};
+                        vp[k + 4] = f2{tB[k * C3_LW + 4], tB[(k + 1) * C3_LW + 4]};
+                    }
+                    vp[3] = f2{tA[3 * C3_LW + 4], tB[4]};
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        va[r] = f2{t[r * C3_LW + 0], t[r * C3_LW + 1]};
+                        vb[r] = f2{t[r * C3_LW + 2], t[r * C3_LW + 3]};
+                        vc[r] = t[r * C3_LW + 4];
+                    }
+                }
+                if constexpr (SKIP) {
+                    // The lanes' 5-column windows overlap, so a lane tests only its columns 0 and 4 of all 8 rows: lanes
+                    // 0...63 cover columns 0...63 and 4...67.  Magnitude bits only: -0 is zero; a denormal, an Inf or a NaN
+                    // is not.  The test is on the channel number and a ballot, so the branch is wave-uniform; staging, DMA,
+                    // waits and barriers are outside this loop and unaffected.
+                    if ((C3_SPARSE >> (c * C3_MC + m)) & 1u) {
+                        unsigned bits = 0;
+#pragma unroll
+                        for (int r = 0; r < 8; ++r) bits |= __float_as_uint(va[r].x);
+#pragma unroll
+                        for (int k = 0; k < 8; k += 2) bits |= __float_as_uint(vp[k].x) | __float_as_uint(vp[k].y);
+                        if (__builtin_amdgcn_ballot_w64((bits & 0x7fffffffu) != 0u) == 0ull) continue;
+                    }
                 }
                 const float* wrow = w3s + (c * C3_MC + m) * 30;
                 // four independent fp64 chains (one per pixel) advance tap by tap, so consecutive v_add_f64 never
@@ -1278,10 +1286,14 @@ __global__ __launch_bounds__(256, SDMA ? 6 : 3) void k_conv3(
                     const f2 wa = f2{wrow[dy * 6 + 0], wrow[dy * 6 + 1]};
                     const f2 wb = f2{wrow[dy * 6 + 2], wrow[dy * 6 + 3]};
                     const float wc = wrow[dy * 6 + 4];
+                    f2 pc01, pc23;
+                    if constexpr (SDMA) { pc01 = f2{wc, wc} * vp[dy]; pc23 = f2{wc, wc} * vp[dy + 2]; }
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const f2 pa = wa * va[q + dy], pb = wb * vb[q + dy];
-                        const float pc = wc * vc[q + dy];
+                        float pc;
+                        if constexpr (SDMA) pc = q == 0 ? pc01.x : q == 1 ? pc01.y : q == 2 ? pc23.x : pc23.y;
+                        else pc = wc * vc[q + dy];
                         // tap (0,0): "0.0 + p" is p (a -0 differs from the reference's +0 only until it is folded
                         // into the fp32 running sum, which can never be -0)
                         a[q] = (dy == 0) ? (double)pa.x : a[q] + (double)pa.x;
@@ -1433,178 +1445,6 @@ __global__ __launch_bounds__(256) void k_conv3_fast(
 }
 
 #endif  // SRCNN_STRICT_ONLY
-
-// =============================================================================================
-// conv3, strict, skipping all-zero channel windows: the production layer-3 kernel (SRCNN_CONV3_SKIP, default 1).
-// It is k_conv3<true, false, false, true> -- same tile, same 2-channel LDS-DMA stages, same waits and barriers, same
-// arithmetic in the same order, written out for that one instance -- plus one test per candidate channel.  k_conv3 itself is
-// untouched and is what SRCNN_CONV3_SKIP=0 runs.
-//
-// Why a kernel of its own and not a branch inside that instance, which is where the test belongs: k_conv3's text is pinned.
-// build.kernel_source_sha("k_conv3") covers the template, the C3_* constants and launch_conv3, and tests/test_rect_abi.py
-// (read by test_rgb_rect_abi.py and test_yuv_rect_abi.py) asserts its value, so none of the three can be edited.  The price:
-// layer 3's staging, waits and barriers exist twice and must be kept in step by hand (tests/test_gpu_conv3_skip.py runs both
-// kernels on the same planes and compares both with the oracle), and the strict tier has one form more than "production + one
-// fallback".  When that pin next moves, fold this kernel back into k_conv3 as `if (skip && ...)` with `skip` a kernel argument.
-// This kernel has a fingerprint of its own, kernel_source_sha("k_conv3_sparse"), which also covers launch_layer3; the traffic
-// record bench.py quotes is held to it (tools/summarize_profiles.py).
-//
-// C3_SPARSE: layer-2 channels (bit m = channel m) that are often all zero over everything a wave reads, its 68 x 8 window
-// (64 columns x 4 rows + 2 halo).  The kernel tests these, and only these, and skips the channel's arithmetic for a wave
-// that has just SEEN the window all +-0, so ANY set is correct; it only has to be good.  tools/conv3_zero_windows.py counts
-// such windows per channel (profiles/conv3_zero_windows.txt: 26 on nearly every window of every input, 29 / 13 / 1 on
-// 78 / 47 / 30 % of the smooth generator's; no other channel reaches 25 % on any input).
-// =============================================================================================
-constexpr unsigned C3_SPARSE = 0x24002002u;       // 1 13 26 29
-
-__global__ __launch_bounds__(256, 6) void k_conv3_sparse(
-    const float* __restrict__ C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows,
-    float* __restrict__ out, int out_row0, int out_rows)
-{
-    constexpr int C3_MC = c3_mc(true);
-    __shared__ float tile[2][C3_MC * C3_CH];
-    __shared__ __attribute__((aligned(16))) float w3s[C2N * 30];      // [m][dy][6]: (w0,w1) (w2,w3) w4 pad
-
-    const int tx0 = blockIdx.x * C3_TW;
-    const int ty0 = out_row0 + blockIdx.y * C3_TH;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int c2_last = c2_row_base + c2_rows - 1;
-    const int wave_e0 = __builtin_amdgcn_readfirstlane(tid & ~63);
-#pragma unroll
-    for (int i = 0; i < (C2N * 30 + 255) / 256; ++i) {
-        const int e = tid + i * 256;
-        if (e < C2N * 30) rs_dma_dword(cW.w3p + e, w3s + i * 256 + wave_e0);
-    }
-
-    // staging geometry (fixed per thread), as in k_conv3
-    const int bx = min(tx0 + lane, W - 1);                                  // body column
-    const int hq = tid & 3;                                                 // halo: 4 columns per staged row
-    const int hx = clampi(tx0 + (hq < 2 ? hq - 2 : 62 + hq), 0, W - 1);     // image cols tx0-2,tx0-1,tx0+64,tx0+65
-    const int hlc = hq < 2 ? hq : 64 + hq;                                  // LDS cols 0,1,66,67
-    auto row_of = [&](int r) {                // staged row r (0..LH-1) -> row inside the c2 buffer
-        int gy = clampi(ty0 + r - 2, 0, H - 1);
-        gy = clampi(gy, c2_row_base, c2_last);
-        return gy - c2_row_base;
-    };
-    unsigned boff[C3_LH / 4];                                               // BYTE offsets inside a plane
-#pragma unroll
-    for (int j = 0; j < C3_LH / 4; ++j) boff[j] = ((unsigned)row_of(4 * j + wv) * (unsigned)W + (unsigned)bx) * 4u;
-    const int wv_s = __builtin_amdgcn_readfirstlane(wv);
-    float halo4[C3_MC];
-    const int h4row = min(tid >> 2, C3_LH - 1);
-    const unsigned h4off = ((unsigned)row_of(h4row) * (unsigned)W + (unsigned)hx) * 4u;
-    auto issue_dma = [&](int mc, float* dst) {     // global -> LDS for the chunk starting at channel mc
-        if (tid < C3_LH * 4) {
-#pragma unroll
-            for (int m = 0; m < C3_MC; ++m)
-                halo4[m] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(C2 + (size_t)(mc + m) * plane_stride) + h4off);
-        }
-#pragma unroll
-        for (int m = 0; m < C3_MC; ++m) {
-            const unsigned long long pb = reinterpret_cast<unsigned long long>(C2 + (size_t)(mc + m) * plane_stride);
-            const unsigned ub_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pb >> 32));
-            const unsigned ub_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pb);
-            const unsigned long long ub = ((unsigned long long)ub_hi << 32) | (unsigned long long)ub_lo;
-#pragma unroll
-            for (int j = 0; j < C3_LH / 4; ++j)
-                rs_dma_dword_s(reinterpret_cast<const void*>(ub), boff[j], dst + (wv_s + 4 * (m * (C3_LH / 4) + j)) * C3_LW + 2);
-        }
-    };
-    auto land_dma = [&](float* dst) {              // the halo registers -> LDS; every DMA of this wave has landed
-        if (tid < C3_LH * 4) {
-#pragma unroll
-            for (int m = 0; m < C3_MC; ++m) dst[m * C3_CH + h4row * C3_LW + hlc] = halo4[m];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-
-    float sum[4] = {0.f, 0.f, 0.f, 0.f};
-    issue_dma(0, tile[0]);
-    land_dma(tile[0]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the weight image's DMA
-    __syncthreads();
-
-    const int offA = (wv * 4) * C3_LW + lane;             // the lane's two LDS row bases (rows 0-3 and 4-7 of its window)
-    int offB = offA + 4 * C3_LW;
-    asm volatile("" : "+v"(offB));
-
-#pragma unroll 1
-    for (int c = 0; c < C2N / C3_MC; ++c) {
-        const float* cur = tile[c & 1];
-        if (c + 1 < C2N / C3_MC) issue_dma((c + 1) * C3_MC, tile[(c + 1) & 1]);
-#pragma unroll 1
-        for (int m = 0; m < C3_MC; ++m) {
-            typedef float f2 __attribute__((ext_vector_type(2)));
-            const float* tA = cur + m * C3_CH + offA;
-            const float* tB = cur + m * C3_CH + offB;
-            f2 va[8], vb[8], vp[7];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                va[r] = f2{tA[r * C3_LW + 0], tA[r * C3_LW + 1]};
-                vb[r] = f2{tA[r * C3_LW + 2], tA[r * C3_LW + 3]};
-                va[r + 4] = f2{tB[r * C3_LW + 0], tB[r * C3_LW + 1]};
-                vb[r + 4] = f2{tB[r * C3_LW + 2], tB[r * C3_LW + 3]};
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                vp[k] = f2{tA[k * C3_LW + 4], tA[(k + 1) * C3_LW + 4]};
-                vp[k + 4] = f2{tB[k * C3_LW + 4], tB[(k + 1) * C3_LW + 4]};
-            }
-            vp[3] = f2{tA[3 * C3_LW + 4], tB[4]};
-            // A channel of C3_SPARSE whose activations are all +-0 over the wave's 68 x 8 window is skipped by that wave.  The
-            // lanes' 5-column windows overlap, so a lane tests only its columns 0 and 4 of all 8 rows: lanes 0...63 cover
-            // columns 0...63 and 4...67.  Magnitude bits only: -0 is zero; a denormal, an Inf or a NaN is not.  The test is on
-            // the channel number and a ballot, so the branch is wave-uniform; staging, DMA, waits and barriers are outside this
-            // loop and unaffected.
-            // Skipping changes no stored bit: every lane's 100 products are (+-0) x (a finite weight; tests/
-            // test_gpu_conv3_skip.py checks the table) = +-0, so each fp64 accumulator a[q] is +-0, and
-            // (float)((double)sum + +-0) is sum for every nonzero or NaN sum.  sum itself starts at +0.0f and is only ever the
-            // rounded result of an fp64 add that began from +0, which round-to-nearest never makes -0, so (+0) + (-0) = +0 is
-            // sum as well.  NaN or Inf in any other channel is not touched.
-            if ((C3_SPARSE >> (c * C3_MC + m)) & 1u) {
-                unsigned bits = 0;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) bits |= __float_as_uint(va[r].x);
-#pragma unroll
-                for (int k = 0; k < 8; k += 2) bits |= __float_as_uint(vp[k].x) | __float_as_uint(vp[k].y);
-                if (__builtin_amdgcn_ballot_w64((bits & 0x7fffffffu) != 0u) == 0ull) continue;
-            }
-            const float* wrow = w3s + (c * C3_MC + m) * 30;
-            double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int dy = 0; dy < 5; ++dy) {
-                const f2 wa = f2{wrow[dy * 6 + 0], wrow[dy * 6 + 1]};
-                const f2 wb = f2{wrow[dy * 6 + 2], wrow[dy * 6 + 3]};
-                const f2 wc = f2{wrow[dy * 6 + 4], wrow[dy * 6 + 4]};
-                const f2 pc01 = wc * vp[dy], pc23 = wc * vp[dy + 2];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f2 pa = wa * va[q + dy], pb = wb * vb[q + dy];
-                    const float pc = q == 0 ? pc01.x : q == 1 ? pc01.y : q == 2 ? pc23.x : pc23.y;
-                    a[q] = (dy == 0) ? (double)pa.x : a[q] + (double)pa.x;
-                    a[q] = a[q] + (double)pa.y;
-                    a[q] = a[q] + (double)pb.x;
-                    a[q] = a[q] + (double)pb.y;
-                    a[q] = a[q] + (double)pc;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sum[q] = (float)((double)sum[q] + a[q]);
-        }
-        if (c + 1 < C2N / C3_MC) land_dma(tile[(c + 1) & 1]);
-        __syncthreads();
-    }
-    const int x = tx0 + lane;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int row = ty0 + wv * 4 + q;
-        if (x < W && row < H && row < out_row0 + out_rows) {
-            float v = sum[q] + cW.b3;
-            v = fminf(fmaxf(v, 0.f), 255.f);
-            out[(size_t)(row - out_row0) * W + x] = v;
-        }
-    }
-}
 
 // =============================================================================================
 // Unfused layer 1 and layer 2 (stage-level entry points; not used by the hot path).
@@ -1895,64 +1735,40 @@ void launch_conv12_mfma(const float* Y, int W, int H, int y_row_base, int y_rows
 #undef CONV12_GO
 }
 
+// Layer 3 as every caller launches it: one grid of 64 x 16 tiles, one argument list, the instance picked here.  The production
+// strict kernel is the LDS-DMA instance that skips all-zero channel windows (SRCNN_CONV3_SKIP, default 1); SRCNN_CONV3_SKIP=0,
+// SRCNN_CONV3_WDMA=0 and planes of 4 GiB or more take the instances without it.
 void launch_conv3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out,
                   int out_row0, int out_rows, int relax, hipStream_t s)
 {
     if (out_rows <= 0) return;
+    const dim3 grid(cdiv(W, C3_TW), cdiv(out_rows, C3_TH));
+#define CONV3_GO(WBD, ...) hipLaunchKernelGGL((k_conv3<__VA_ARGS__>), grid, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows, \
+                                              out, out_row0, out_rows, WBD)
+    const bool big = (size_t)c2_rows * (size_t)W * sizeof(float) >= ((size_t)1 << 32);      // per-plane byte offsets beyond 32 bits
 #ifndef SRCNN_STRICT_ONLY
-    const bool strict = !(relax & (RELAX_L3_X64 | RELAX_L3_F32));
-    const bool wide_planes = (size_t)c2_rows * (size_t)W * sizeof(float) >= ((size_t)1 << 32);
     if (relax & RELAX_L3_X64) {
-        const dim3 gx(cdiv(W, 64), cdiv(out_rows, 16));
-        if (wide_planes)
-            hipLaunchKernelGGL((k_conv3<true, true, true>), gx, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows, out, out_row0, out_rows, 0);
-        else
-            hipLaunchKernelGGL((k_conv3<true, false, true>), gx, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows, out, out_row0, out_rows, 0);
+        if (big) CONV3_GO(0, true, true, true); else CONV3_GO(0, true, false, true);
         return;
     }
-    if (!strict) {
-        dim3 gridf(cdiv(W, CF_TW), cdiv(out_rows, CF_TH));
-        hipLaunchKernelGGL(k_conv3_fast, gridf, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows, out,
-                           out_row0, out_rows);
-        return;
-    }
-#else
-    (void)relax;
-#endif
-    dim3 grid(cdiv(W, 64), cdiv(out_rows, 16));
-    const bool force_wide = settings().conv3_off64;      // test hook
-    const int wdma = settings().conv3_wdma ? 1 : 0;
-    const bool wide = force_wide || (size_t)c2_rows * (size_t)W * sizeof(float) >= ((size_t)1 << 32);     // per-plane byte offsets beyond 32 bits
-    if (!wide && wdma)
-        hipLaunchKernelGGL((k_conv3<true, false, false, true>), grid, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows,
-                           out, out_row0, out_rows, 1);
-    else if (!wide)
-        hipLaunchKernelGGL((k_conv3<true, false>), grid, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows,
-                           out, out_row0, out_rows, wdma);
-    else
-        hipLaunchKernelGGL((k_conv3<true, true>), grid, dim3(256), 0, s, C2, plane_stride, W, H, c2_row_base, c2_rows,
-                           out, out_row0, out_rows, wdma);
-}
-
-// Layer 3 as every caller launches it.  The production strict kernel skips all-zero channel windows (k_conv3_sparse); what
-// that kernel does not cover -- a non-parity tier, planes of 4 GiB or more, SRCNN_CONV3_WDMA=0 -- and SRCNN_CONV3_SKIP=0 go
-// to launch_conv3.  Same grid, block and arguments either way.
-void launch_layer3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out,
-                   int out_row0, int out_rows, int relax, hipStream_t s)
-{
-    if (out_rows <= 0) return;
-#ifndef SRCNN_STRICT_ONLY
-    const bool strict = !(relax & (RELAX_L3_X64 | RELAX_L3_F32));
-#else
-    const bool strict = true;
-#endif
-    const bool wide = settings().conv3_off64 || (size_t)c2_rows * (size_t)W * sizeof(float) >= ((size_t)1 << 32);
-    if (strict && !wide && settings().conv3_wdma && settings().conv3_skip) {
-        hipLaunchKernelGGL(k_conv3_sparse, dim3(cdiv(W, C3_TW), cdiv(out_rows, C3_TH)), dim3(256), 0, s, C2, plane_stride, W, H,
+    if (relax & RELAX_L3_F32) {
+        hipLaunchKernelGGL(k_conv3_fast, dim3(cdiv(W, CF_TW), cdiv(out_rows, CF_TH)), dim3(256), 0, s, C2, plane_stride, W, H,
                            c2_row_base, c2_rows, out, out_row0, out_rows);
         return;
     }
-    launch_conv3(C2, plane_stride, W, H, c2_row_base, c2_rows, out, out_row0, out_rows, relax, s);
+#else
+    (void)relax;                     // srcnn_set_mode refuses every other mode in this build
+#endif
+    const bool wide = big || settings().conv3_off64;      // SRCNN_CONV3_OFF64: test hook of the strict instances
+    const int wdma = settings().conv3_wdma ? 1 : 0;
+    if (!wide && wdma) {
+        if (settings().conv3_skip) CONV3_GO(1, true, false, false, true, true); else CONV3_GO(1, true, false, false, true, false);
+    } else if (!wide) {
+        CONV3_GO(wdma, true, false);
+    } else {
+        CONV3_GO(wdma, true, true);
+    }
+#undef CONV3_GO
 }
 
 void launch_conv1_planes(const float* Y, int W, int H, float* C1, hipStream_t s)

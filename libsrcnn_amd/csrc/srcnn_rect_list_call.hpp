@@ -205,7 +205,7 @@ int list_batched(Call& c, const Shell& sh, unsigned dw, unsigned dh, const RectL
             // layer 3 clamps the ACTIVATIONS to the plane's edge: the ring of 2 around a rect that lies outside the plane gets the
             // activation at the clamped coordinate (layer 2 over the replicated input above is not that)
             launch_list_replicate(d, pass.count, end, ws.c2.data(), W, plane, C2N, 2, c.s);
-            launch_layer3(ws.c2.data(), plane, (int)W, (int)H, 0, (int)H, ws.win.data(), 0, (int)H, c.relax(), c.s);
+            launch_conv3(ws.c2.data(), plane, (int)W, (int)H, 0, (int)H, ws.win.data(), 0, (int)H, c.relax(), c.s);
         }
         sh.store(c, p);
         if (const hipError_t e = hipGetLastError(); e != hipSuccess) {

@@ -38,7 +38,7 @@
     X(B, conv12_spread,    "SRCNN_CONV12_SPREAD",    1,     "0/1", "layer 1+2: small launches dealt in quarter tiles over up to 4x more workgroups") \
     X(B, conv3_wdma,       "SRCNN_CONV3_WDMA",       1,     "0/1", "layer 3: packed weight image staged by LDS-DMA vs a plain loop") \
     X(B, conv3_off64,      "SRCNN_CONV3_OFF64",      0,     "0/1", "layer 3: 64-bit plane offsets (chosen automatically for planes of 4 GiB or more)") \
-    X(B, conv3_skip,       "SRCNN_CONV3_SKIP",       1,     "0/1", "layer 3: `k_conv3_sparse`, where a wave skips a layer-2 channel of the candidate set {1, 13, 26, 29} whose activations it has just read as all zero over its 68x8 window, vs `k_conv3`, which always runs all 32") \
+    X(B, conv3_skip,       "SRCNN_CONV3_SKIP",       1,     "0/1", "layer 3: the `SKIP` instance of `k_conv3`, where a wave skips a layer-2 channel of the candidate set {1, 13, 26, 29} whose activations it has just read as all zero over its 68x8 window, vs the instance without the test, which always runs all 32") \
     X(B, rs_dma,           "SRCNN_RS_DMA",           1,     "0/1", "resampler: `k_rs2d_dma` (source patch by LDS-DMA) vs `k_rs2d` for plane sources") \
     X(I, rs_tpb,           "SRCNN_RS_TPB",           0,     "0 = auto, 1...16", "resampler: row tiles a block marches through") \
     X(B, resample_2pass,   "SRCNN_RESAMPLE_2PASS",   0,     "0/1", "resampler: always the two generic passes (`k_resample_cols/rows`, what down-scales use); implies the unfused colour shell") \

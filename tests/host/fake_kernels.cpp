@@ -499,12 +499,6 @@ void launch_conv3(const float* C2, size_t plane_stride, int W, int H, int c2_row
     });
 }
 
-void launch_layer3(const float* C2, size_t plane_stride, int W, int H, int c2_row_base, int c2_rows, float* out, int out_row0,
-                   int out_rows, int relax, hipStream_t s)
-{
-    launch_conv3(C2, plane_stride, W, H, c2_row_base, c2_rows, out, out_row0, out_rows, relax, s);
-}
-
 // ---- the window kernels of the rect call (srcnn_window.h): the arithmetic of the two passes above, over a window ----
 
 // A strided block of w x rows floats is declared row by row: the floats between two rows belong to the caller (the canary columns

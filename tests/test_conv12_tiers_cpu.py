@@ -1,8 +1,10 @@
 """CPU checks of the premises of k_conv12_mfma's nested zero tiers (the GPU side is tests/test_gpu_conv12_tiers.py): the tier
 masks in the kernel source are a nested chain that starts at M_DEAD and are the ones tools/conv12_zero_segments.py printed; the
 exactness argument's two facts about the weight table hold (no layer-2 bias is +-0, every layer-2 weight is finite); the three
-pinned kernel fingerprints are the recorded ones, k_conv12_mfma's covers the tiers and run_conv12, and the committed traffic
-record was measured on this text."""
+pinned kernel fingerprints are the recorded ones, k_conv12_mfma's covers the tiers and run_conv12, k_conv3's covers C3_SPARSE and
+launch_conv3, and the committed traffic record was measured on this text.  k_conv3's pin moved once, on purpose, when
+the written-out copy of its
+skip instance was folded into the template instruction for instruction (profiles/conv3_fold_isa.txt)."""
 import json
 import os
 import re
@@ -14,7 +16,7 @@ from libsrcnn_amd import build
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PINNED = {
     "k_conv12_mfma": "94857eddbb2a8296a76ec6a18246f0288de6590de38bfd8a5f647015ee1ee39a",
-    "k_conv3": "8f0b7e652c0cb756f84cfcb4c4c087ecf194afc30c362529bc70a23bf8764bd9",
+    "k_conv3": "4d4511830f635b4324fe30ab3cc2c5f8861b2dac0d85fb0c7ac48db46b7fa46d",
     "k_rs2d_dma": "adef7f27470d21d8aa7396a314ed8a758b2707fa87b705cbb289ae66fd085030",
 }
 
@@ -72,8 +74,8 @@ def test_pinned_fingerprints_are_unchanged():
         assert build.kernel_source_sha(name) == sha, name
 
 
-def _sha_of_modified_copy(monkeypatch, tmp_path, file, old, new):
-    """kernel_source_sha("k_conv12_mfma") of a copy of the sources in which `old` (which occurs once) reads `new`"""
+def _sha_of_modified_copy(monkeypatch, tmp_path, file, old, new, name="k_conv12_mfma"):
+    """kernel_source_sha(name) of a copy of the sources in which `old` (which occurs once) reads `new`"""
     for f in ("srcnn_kernels.hip", "srcnn_capi.cpp"):
         text = open(os.path.join(build.CSRC, f)).read()
         if f == file:
@@ -81,7 +83,7 @@ def _sha_of_modified_copy(monkeypatch, tmp_path, file, old, new):
             text = text.replace(old, new)
         (tmp_path / f).write_text(text)
     monkeypatch.setattr(build, "CSRC", str(tmp_path))
-    return build.kernel_source_sha("k_conv12_mfma")
+    return build.kernel_source_sha(name)
 
 
 def test_one_fingerprint_covers_the_tiers_and_run_conv12(monkeypatch, tmp_path):
@@ -98,11 +100,25 @@ def test_one_fingerprint_covers_the_tiers_and_run_conv12(monkeypatch, tmp_path):
     assert build.kernel_source_sha("k_conv12_mfma") == sha
 
 
+def test_one_fingerprint_covers_the_skip_instance_and_launch_conv3(monkeypatch, tmp_path):
+    """The instance that skips all-zero channel windows is k_conv3's: there is no second kernel and no second fingerprint, and
+    the one fingerprint moves with the candidate set and with the launcher that picks the instance."""
+    assert build.kernel_source_sha("k_conv3_sparse") is None
+    sha = build.kernel_source_sha("k_conv3")
+    assert _sha_of_modified_copy(monkeypatch, tmp_path, "srcnn_kernels.hip", "C3_SPARSE = 0x24002002u;", "C3_SPARSE = 0x24002003u;",
+                                 "k_conv3") not in (None, sha)
+    monkeypatch.undo()
+    assert _sha_of_modified_copy(monkeypatch, tmp_path, "srcnn_kernels.hip", "if (settings().conv3_skip) CONV3_GO(",
+                                 "if (!settings().conv3_skip) CONV3_GO(", "k_conv3") not in (None, sha)
+    monkeypatch.undo()
+    assert build.kernel_source_sha("k_conv3") == sha
+
+
 def test_traffic_record_carries_the_trees_fingerprints():
     """bench.py quotes roofline.traffic and whole_path only from a record taken on this text: profiles/r06_pmc_conv12.json must
     carry the tree's fingerprints, at top level (k_conv12_mfma) and for every kernel of `path`."""
     rec = json.load(open(os.path.join(ROOT, "profiles", "r06_pmc_conv12.json")))
     assert rec["kernel"] == "k_conv12_mfma" and rec["kernel_source_sha256"] == build.kernel_source_sha("k_conv12_mfma")
-    assert set(rec["path"]) == {"k_conv12_mfma", "k_conv3_sparse", "k_rs2d_dma"}
+    assert set(rec["path"]) == {"k_conv12_mfma", "k_conv3", "k_rs2d_dma"}
     for name, entry in rec["path"].items():
         assert entry["kernel_source_sha256"] == build.kernel_source_sha(name), name

@@ -1,6 +1,6 @@
-"""The production strict layer-3 kernel (k_conv3_sparse) lets a wave skip a layer-2 channel of C3_SPARSE (in
-srcnn_kernels.hip) whose activations it has just read as all +-0 over its 68 x 8 window; SRCNN_CONV3_SKIP=0 runs k_conv3,
-which never skips.  The
+"""The production strict layer-3 kernel (k_conv3<true, false, false, true, SKIP = true>) lets a wave skip a layer-2 channel of
+C3_SPARSE (in srcnn_kernels.hip) whose activations it has just read as all +-0 over its 68 x 8 window; SRCNN_CONV3_SKIP=0 runs
+the instance with SKIP = false, which never skips.  The
 result must stay the oracle's bit for bit whether a wave skips or not, so the planes below are built -- through the
 stage-level conv3 call on caller-provided planes -- to put every candidate channel on both sides of that decision for waves
 in the interior, on tile seams, in the ragged right / bottom tiles and at the clamped image border.
@@ -98,13 +98,15 @@ def test_mask_matches_the_source_and_the_committed_count_and_layer3_weights_are_
 
 
 def test_both_layer3_kernels_are_in_both_builds():
-    """CPU: the skipping kernel and the one SRCNN_CONV3_SKIP=0 runs are compiled into the full and the strict-only library."""
+    """CPU: the skipping instance of k_conv3 and the one SRCNN_CONV3_SKIP=0 runs are compiled into the full and the strict-only
+    library; the written-out copy of the former (see the last line) is in neither."""
     import libsrcnn_amd as S
     from libsrcnn_amd import build
     strict, _ = build.build_strict_only(verbose=False)
     for path in (S.LIB_PATH, strict):
         blob = open(path, "rb").read()
-        assert b"k_conv3_sparse" in blob and b"k_conv3ILb1ELb0ELb0ELb1" in blob, path
+        assert b"k_conv3ILb1ELb0ELb0ELb1ELb1E" in blob and b"k_conv3ILb1ELb0ELb0ELb1ELb0E" in blob, path
+        assert b"k_conv3_sparse" not in blob, path
 
 
 @pytest.mark.gpu

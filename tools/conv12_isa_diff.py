@@ -9,7 +9,8 @@ whether the .amdhsa_ block and the multiset of opcodes are the same on both side
 Each tree's csrc/srcnn_kernels.hip is compiled device-only to assembly with the Makefile's HIPFLAGS.  A kernel's text runs from
 its label to the end of its .amdhsa_kernel block, so register counts, scratch, LDS and kernarg size are compared too.  Comments
 go, the kernel's own symbol becomes K and block labels lose their function number.  k_conv12_tiers and k_conv12_mfma<R, LD>
-are compared with the k_conv12_mfma<R, LD, TIERS> that replaced them.  Needs hipcc; no GPU."""
+are compared with the k_conv12_mfma<R, LD, TIERS> that replaced them, k_conv3_sparse and k_conv3<STRICT, OFF64, X64, SDMA> with
+the k_conv3<STRICT, OFF64, X64, SDMA, SKIP> that replaced them (profiles/conv3_fold_isa.txt).  Needs hipcc; no GPU."""
 import collections
 import difflib
 import os
@@ -37,7 +38,12 @@ def key(sym):
     if "k_conv12_tiers" in sym:
         return "k_conv12_mfma<0,1,1>"
     m = re.search(r"k_conv12_mfmaILi(\d)ELb(\d)E(?:Lb(\d)E)?EEv", sym)
-    return "k_conv12_mfma<%s,%s,%s>" % (m.group(1), m.group(2), m.group(3) or "0") if m else sym
+    if m:
+        return "k_conv12_mfma<%s,%s,%s>" % (m.group(1), m.group(2), m.group(3) or "0")
+    if "k_conv3_sparse" in sym:
+        return "k_conv3<1,0,0,1,1>"
+    m = re.search(r"k_conv3ILb(\d)ELb(\d)ELb(\d)ELb(\d)E(?:Lb(\d)E)?EEv", sym)
+    return "k_conv3<%s,%s,%s,%s,%s>" % (m.group(1), m.group(2), m.group(3), m.group(4), m.group(5) or "0") if m else sym
 
 
 def kernels(asm):
@@ -65,7 +71,7 @@ def main(a, b, source=None):
             print("%-60s %5d / %5d lines, %d differ; .amdhsa_ block %s, opcode multiset %s (%d)" % (
                 k[:60], len(ka[k]), len(kb[k]), len(d), "same" if ra == rb else "DIFFERS", "same" if oa == ob else "DIFFERS", sum(oa.values())))
             same += not d
-        elif d or "k_conv12" in k:
+        elif d or "k_conv12" in k or "k_conv3<" in k:
             print("%-60s %5d / %5d lines, %d differ" % (k[:60], len(ka[k]), len(kb[k]), len(d)))
             for l in d[:20]:
                 print("    " + l)

@@ -39,13 +39,11 @@ def short(name):
     if "k_conv12_mfma<" in name:          # first template argument = RELAX mask: 0 strict, 3 fast tier, 1 / 2 single-layer relaxations
         r = name.split("k_conv12_mfma<")[1].split(",")[0].strip()
         return "k_conv12_mfma" + {"0": " [strict]", "3": " [fast tier]"}.get(r, " [relaxed %s]" % r)
-    if "k_conv3_sparse" in name:        # the strict path's default layer-3 kernel (not a template: no "<true" to go by)
-        return "k_conv3_sparse [strict]"
-    if "k_conv3<" in name:              # k_conv3<STRICT, OFF64, X64, SDMA>: the third argument marks the relaxed-x64 experiment
-        targs = name.split("k_conv3<")[1].split(">")[0].replace(" ", "").split(",")
+    if "k_conv3<" in name:              # k_conv3<STRICT, OFF64, X64, SDMA, SKIP>: the third argument marks the relaxed-x64 experiment,
+        targs = name.split("k_conv3<")[1].split(">")[0].replace(" ", "").split(",")      # the fifth the strict path's default instance
         if len(targs) >= 3 and targs[2] == "true":
             return "k_conv3 [relaxed x64]"
-        return "k_conv3 [strict]"
+        return "k_conv3 [strict, skip]" if targs[3:5] == ["true", "true"] else "k_conv3 [strict]"
     if "k_rs2d_dma" in name:
         return "k_rs2d_dma [plane -> plane, LDS-DMA]"
     if "k_rs2d<" in name:
@@ -114,9 +112,9 @@ if pmc:
         # (per FRAME: per-launch average x launches per frame)
         path = {"k_conv12_mfma": {"fetch_bytes": fetch * lpf12, "write_bytes": write * lpf12, "launches_per_frame": lpf12,
                           "kernel_source_sha256": _b.kernel_source_sha("k_conv12_mfma")}}
-        # layer 3 under the name and the fingerprint of the kernel that RAN (k_conv3_sparse, or k_conv3 with SRCNN_CONV3_SKIP=0):
-        # bench.py holds every entry of `path` to build.kernel_source_sha(its key)
-        for kname, key in (("k_conv3_sparse", "k_conv3_sparse [strict]"), ("k_conv3", "k_conv3 [strict]"),
+        # layer 3 under "k_conv3", whichever strict instance RAN (the skip one, or with SRCNN_CONV3_SKIP=0 the one without the test):
+        # one template, one fingerprint; bench.py holds every entry of `path` to build.kernel_source_sha(its key)
+        for kname, key in (("k_conv3", "k_conv3 [strict, skip]" if "k_conv3 [strict, skip]" in pmc else "k_conv3 [strict]"),
                            ("k_rs2d_dma", "k_rs2d_dma [plane -> plane, LDS-DMA]")):
             kk = pmc.get(key)
             if kk and "FETCH_SIZE" in kk and "WRITE_SIZE" in kk:
