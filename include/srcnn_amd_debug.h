@@ -39,6 +39,14 @@ int srcnn_axis_table(int filter, unsigned dst_len, unsigned src_len, int* left, 
  * s_memtime stamps of workgroup 0 (d_dbg: 8 x 64 x 4 uint64, or NULL).  Used by tools/fused_timeline.py. */
 int srcnn_fused_diag(const float* d_up, unsigned w, unsigned h, float* d_out, unsigned long long* d_dbg, void* stream);
 
+/* Test hook: the fused non-parity kernel on caller-given weights (tests/test_gpu_fused_f16_exact.py holds it bit for bit to a
+ * restatement of its arithmetic on exactly summable inputs).  weights: host, 8129 floats in the blob order b1, W1, b2, W2, b3, W3,
+ * packed by the product's own packers into a temporary device image; NULL: the product's image.  d_up holds rows [up_row0,
+ * up_row0 + up_rows) of an already upscaled w x h plane, d_out receives output rows [out_row0, out_row0 + out_rows); SRCNN_E_ARG
+ * unless the staged rows cover those rows +-2 (layer 3) +-4 (layer 1), cut at the borders.  Synchronous on `stream`. */
+int srcnn_debug_fused_f16(const float* weights, const float* d_up, unsigned w, unsigned h, unsigned up_row0, unsigned up_rows,
+                          float* d_out, unsigned out_row0, unsigned out_rows, void* stream);
+
 /* Test hook: number of contribution tables currently cached (bounded, only unreferenced tables are evicted) and
  * of ProcessSRCNN lanes created so far (at most 4 per context), both summed over the contexts. */
 int srcnn_debug_counts(int* tables, int* lanes);

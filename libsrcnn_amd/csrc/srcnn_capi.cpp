@@ -185,9 +185,9 @@ const uint32_t kWeightBits[kWeightCount] = {
 #include "srcnn_weights.inc"
 };
 
-void build_dev_weights(DevWeights& d)
+// w: 8129 floats in the blob order b1, W1, b2, W2, b3, W3 -- the product's, or a caller's (srcnn_debug_fused_f16)
+void build_dev_weights(DevWeights& d, const float* w = reinterpret_cast<const float*>(kWeightBits))
 {
-    const float* w = reinterpret_cast<const float*>(kWeightBits);
     const float* b1 = w;
     const float* w1 = b1 + 64;          // [k][i][j]      (src/convdata.h:32-674)
     const float* b2 = w1 + 64 * 81;
@@ -1776,6 +1776,46 @@ int srcnn_fused_diag(const float* d_up, unsigned w, unsigned h, float* d_out, un
     if (!cx) return SRCNN_E_NODEVICE;
     launch_fused_f16(d_up, (int)w, (int)h, 0, (int)h, d_out, 0, (int)h, cx->fused_w.data(), cx->num_cus, (hipStream_t)stream, d_dbg);
     HIP_TRY(hipGetLastError());
+    return SRCNN_OK;
+#endif
+}
+
+// Test hook (tests/test_gpu_fused_f16_exact.py): the fused fp16 kernel, through the product's launcher, on output rows
+// [out_row0, +out_rows) of an already upscaled w x h plane of which d_up holds rows [up_row0, +up_rows) -- with the product's
+// weight image, or with one built here from a caller's blob by the product's own two packers.  Synchronous: the temporary
+// weight image is freed before the call returns.
+int srcnn_debug_fused_f16(const float* weights, const float* d_up, unsigned w, unsigned h, unsigned up_row0, unsigned up_rows,
+                          float* d_out, unsigned out_row0, unsigned out_rows, void* stream)
+{
+    int rc;
+    if ((rc = check_plane(d_up, w, h, d_out))) return rc;
+    if (up_rows == 0 || out_rows == 0 || up_row0 >= h || up_rows > h - up_row0 || out_row0 >= h || out_rows > h - out_row0)
+        return fail(SRCNN_E_ARG, "srcnn_debug_fused_f16: empty row range or rows outside the plane");
+    const HaloSpan v = y_path_halo(h, out_row0, out_row0 + out_rows);
+    if (up_row0 > v.ua || up_row0 + up_rows < v.ub)
+        return fail(SRCNN_E_ARG, "srcnn_debug_fused_f16: staged rows [%u,%u) do not cover the halo [%u,%u) of output rows [%u,%u)", up_row0,
+                    up_row0 + up_rows, v.ua, v.ub, out_row0, out_row0 + out_rows);
+#ifdef SRCNN_STRICT_ONLY
+    (void)weights; (void)stream;
+    return fail(SRCNN_E_UNSUPPORTED, "strict-only build: the fused fp16 kernel is not compiled in");
+#else
+    Ctx* cx = ctx_for_stream(stream);
+    if (!cx) return SRCNN_E_NODEVICE;
+    DevBuf<FusedF16Weights> image;
+    const FusedF16Weights* d_blob = cx->fused_w.data();
+    if (weights) {
+        auto dw = std::make_unique<DevWeights>();
+        build_dev_weights(*dw, weights);
+        auto fw = std::make_unique<FusedF16Weights>();
+        build_fused_f16_weights(*dw, *fw);
+        if ((rc = image.grow(1))) return rc;
+        if ((rc = copy_h2d_any(*cx, image.data(), fw.get(), sizeof(FusedF16Weights), (hipStream_t)stream))) return rc;
+        d_blob = image.data();
+    }
+    launch_fused_f16(d_up, (int)w, (int)h, (int)up_row0, (int)up_rows, d_out, (int)out_row0, (int)out_rows, d_blob, cx->num_cus,
+                     (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(wait_stream((hipStream_t)stream));        // the image is freed on return
     return SRCNN_OK;
 #endif
 }

@@ -8,6 +8,11 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# Test hooks that include/srcnn_amd_debug.h declares and the library exports, but the binding does not carry: the one test that
+# needs such a hook drives it through the loaded library handle with argtypes of its own (tests/test_gpu_fused_f16_exact.py).
+# They are in no *_SYMBOLS list of the package -- tests/binding_surface.json pins those lists -- so every test that holds the
+# export table to the lists adds exactly these names.
+HANDLE_ONLY_HOOKS = ["srcnn_debug_fused_f16"]
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +41,8 @@ def test_header_symbols_exported(S):
     assert names == frozen, "stable header and include/srcnn_amd.abi disagree: %s" % (set(names) ^ set(frozen))
     assert sorted(S.STABLE_ABI_SYMBOLS) == frozen, set(S.STABLE_ABI_SYMBOLS) ^ set(frozen)
     debug = [n for n in _declared_functions("srcnn_amd_debug.h") if n not in names]
-    assert sorted(S.DEBUG_SYMBOLS) == debug, set(S.DEBUG_SYMBOLS) ^ set(debug)
+    assert sorted(S.DEBUG_SYMBOLS + HANDLE_ONLY_HOOKS) == debug, set(S.DEBUG_SYMBOLS + HANDLE_ONLY_HOOKS) ^ set(debug)
+    assert not set(HANDLE_ONLY_HOOKS) & set(S.C_ABI_SYMBOLS) and all(n.startswith("srcnn_debug_") for n in HANDLE_ONLY_HOOKS)
     assert not any(n.startswith("srcnn_debug_") or n in ("srcnn_fused_diag", "srcnn_set_relaxation") for n in names), "an instrument in the stable header"
     header = open(os.path.join(ROOT, "include", "srcnn_amd.h")).read()
     assert "#define SRCNN_AMD_ABI_VERSION 5" in header and "SRCNN_MODE_RELAXED" not in header
@@ -59,7 +65,8 @@ def test_exports_are_exactly_the_abi(S):
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", S.LIB_PATH], capture_output=True, text=True, check=True).stdout
     names = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert names == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS), set(names) ^ set(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS)
+    want = sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS + HANDLE_ONLY_HOOKS)
+    assert names == want, set(names) ^ set(want)
 
 
 def test_settings_are_one_table_and_design_md_carries_it(S):

@@ -14,7 +14,8 @@ Layer 2 (bit 2) runs v_mfma_f32_32x32x2f32 with C = acc2.  How the two products 
 device by test_k2_probe: of the three models oracle/srcnn_tiers.c offers, K2_MODEL is the one the hardware follows.
 
 Special values (NaN, Inf, denormals, -0 inputs) are left out: the tiers' statements say nothing about them.
-SRCNN_MODE_FAST_F16 is no part of this: no statement fixes the order inside its 16-deep fp16 MFMA.
+SRCNN_MODE_FAST_F16 is no part of this: no statement fixes the order inside its 16-deep fp16 MFMA.  It is held bit for bit
+where that order cannot show, on exactly summable inputs, in tests/test_gpu_fused_f16_exact.py.
 """
 import contextlib
 

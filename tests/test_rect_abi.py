@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_abi import HANDLE_ONLY_HOOKS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG, E_SCALE, E_NODEVICE, E_UNSUPPORTED = -1, -2, -200, -203
 OLDER = ("srcnn_amd.h", "srcnn_amd_debug.h", "srcnn_amd_yuv.h", "srcnn_amd_yuv_ex.h", "srcnn_amd_yuv_packed.h", "srcnn_amd_rgb.h",
@@ -45,7 +47,7 @@ def test_header_list_binding_and_exports_agree(S):
     assert "#define SRCNN_AMD_RECT_VERSION 1" in header and '#include "srcnn_amd.h"' in header
     exported = _exported(S.LIB_PATH)
     assert set(names) <= set(exported)
-    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS)
+    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS + HANDLE_ONLY_HOOKS)
     assert S.lib().srcnn_rect_abi_version() == 1
 
 

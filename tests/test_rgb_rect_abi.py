@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_abi import HANDLE_ONLY_HOOKS
+
 import test_rect_abi as RA
 from test_rect_abi import _declared, _exported, axis_span, edges
 
@@ -40,7 +42,7 @@ def test_header_list_binding_and_exports_agree(S):
     assert "#define SRCNN_AMD_RGB_RECT_VERSION 1" in header and '#include "srcnn_amd_rgb.h"' in header
     exported = _exported(S.LIB_PATH)
     assert set(names) <= set(exported)
-    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS)
+    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS + HANDLE_ONLY_HOOKS)
     assert S.lib().srcnn_rgb_rect_abi_version() == 1
 
 

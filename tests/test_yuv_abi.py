@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_abi import HANDLE_ONLY_HOOKS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG, E_SCALE, E_NODEVICE, E_UNSUPPORTED = -1, -2, -200, -203
 I420, NV12 = 0, 1
@@ -44,7 +46,7 @@ def test_yuv_header_list_binding_and_exports_agree(S):
     assert "#define SRCNN_YUV_I420 0" in header and "#define SRCNN_YUV_NV12 1" in header
     exported = _exported(S.LIB_PATH)
     assert set(names) <= set(exported)
-    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS)
+    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS + HANDLE_ONLY_HOOKS)
     assert S.lib().srcnn_yuv_abi_version() == 1
 
 

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_abi import HANDLE_ONLY_HOOKS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG, E_SCALE, E_NODEVICE, E_UNSUPPORTED = -1, -2, -200, -203
 PLANAR, SEMI = 0, 1
@@ -53,7 +55,7 @@ def test_header_list_binding_and_exports_agree(S):
         assert line in header, line
     exported = _exported(S.LIB_PATH)
     assert set(names) <= set(exported)
-    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS)
+    assert exported == sorted(S.C_ABI_SYMBOLS + S.CXX_SYMBOLS + HANDLE_ONLY_HOOKS)
     assert S.lib().srcnn_yuv_ex_abi_version() == 1
 
 
